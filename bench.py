@@ -21,12 +21,18 @@ split over the N ranks, every rank runs the fused frame kernel on its rows and t
 exchanged with ONE in-place RCCL all-gather per frame (--scaling weak: --entities rows per rank instead).  Rank 0 also times
 the whole scene alone on its GPU (outside the timed region) and reports it as `single_gpu_same_workload`.
 
-Timing: W warm-up steps, then B blocks of exactly K steps, each bracketed by barrier + synchronize pairs; per block the MAX
-over ranks; `ms_per_step` / `value` come from the MEDIAN block (p10 / p90 / min / max under `blocks`).  B is chosen so that the
-timed blocks cover ~0.4 s (at least 15).  Three further blocks run with per-dispatch HIP events on the kernels (`kernels`,
-`roofline`) and are kept out of the statistics -- binding events to a dispatch fences it off from its neighbours.
+A plain run does what the headline figure needs and nothing more: it sets the workload up, runs W warm-up steps, times ONE block
+of exactly K steps bracketed by barrier + synchronize pairs (the MAX over ranks), writes the last step's outputs if
+--dump-outputs DIR is given (benchlib/outputs.py; the inputs are seeded, so the same arguments give the same arrays) and prints the
+result line: `ms_per_step` = that block / K, `value` = units / step time.  `roofline`, `kernels` and `cpu_baseline` are null / empty.
+
+--full adds everything else.  Timing: W warm-up steps, then B blocks of exactly K steps, each bracketed by barrier + synchronize
+pairs; per block the MAX over ranks; `ms_per_step` / `value` come from the MEDIAN block (p10 / p90 / min / max under `blocks`).  B is
+chosen so that the timed blocks cover ~0.4 s (at least 15).  Three further blocks run with per-dispatch HIP events on the kernels
+(`kernels`, `roofline`) and are kept out of the statistics -- binding events to a dispatch fences it off from its neighbours.  Then
+the live traffic passes, the CPU baselines, the end-to-end stages and the other workloads (N = 1), the single-GPU comparison (N > 1).
 Rank 0 prints ONE compact JSON line (< 4 KB: the contract's keys, benchlib/line.py) as the LAST line of stdout and writes everything
-else it measured -- the other workloads, the CPU thread sweep, the end-to-end stages -- to bench_full.json (repo root and gpurun_out/).
+else it measured -- the other workloads, the CPU thread sweep, the end-to-end stages -- to bench_full.json (repository root).
 DESIGN.md section 5 explains the byte accounting behind `roofline`.  The parts live in benchlib/: one module per workload
 (wl_*.py), the timing loop (measure.py), the CPU baselines (cpu_baseline.py -- the only importer of the oracle), the PCIe-inclusive
 block (end_to_end.py), the live PMC traffic passes (traffic.py) and the result line (line.py).
@@ -42,7 +48,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from benchlib import cpu_baseline as cpu, end_to_end as e2e, line as result_line, traffic  # noqa: E402
+from benchlib import cpu_baseline as cpu, end_to_end as e2e, line as result_line, outputs, traffic  # noqa: E402
 from benchlib.common import PROFILED_BLOCKS, with_args  # noqa: E402
 from benchlib.measure import block_stats, measure, roofline_of  # noqa: E402
 from benchlib.wl_batching import build_batching, build_batching_sorted  # noqa: E402
@@ -67,7 +73,13 @@ def parse():
     ap.add_argument("--views", type=int, default=0, help="camera frusta (default 1; sharded: 4)")
     ap.add_argument("--lights", type=int, default=100_000)
     ap.add_argument("--meshes", type=int, default=10_000)
-    ap.add_argument("--blocks", type=int, default=0, help="timed blocks of --steps steps (0 = enough for ~0.4 s, at least 15)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: B timed blocks and their statistics, per-kernel times and the roofline, the live "
+                         "traffic passes, the CPU baselines, the end-to-end stages, the other workloads, at N > 1 the single-GPU comparison "
+                         "(each still has its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy (benchlib/outputs.py)")
+    ap.add_argument("--blocks", type=int, default=0, help="--full: timed blocks of --steps steps (0 = enough for ~0.4 s, at least 15; 15 with --dump-outputs)")
     ap.add_argument("--unfused", action="store_true", help="flat: mi_propagate + mi_cull instead of the fused kernel")
     ap.add_argument("--inline-compaction", action="store_true",
                     help="launch the VisibleEntities compaction as its own kernel every frame (default: MI_CULL_MORE_FRAMES, the "
@@ -171,6 +183,8 @@ def main():
         workload = "frame" if world == 1 else "sharded"
     if workload in ("frame", "lights", "flat_static", "batching", "batching_sorted") and world > 1:
         raise SystemExit(f"--workload {workload} is a single-GPU workload (replicas only); N > 1 runs `sharded` or `tree`")
+    if args.dump_outputs and workload != "frame":
+        raise SystemExit(f"--dump-outputs: only the `frame` workload says what its outputs are (workload {workload})")
 
     stream = torch.cuda.Stream()
     ctx = api.Context(local_rank, stream.cuda_stream)
@@ -211,24 +225,30 @@ def main():
             tt = torch.tensor([nb], dtype=torch.int64, device="cuda")
             dist.all_reduce(tt, op=dist.ReduceOp.MIN)
             return int(tt.item())
-        times, prof, info = measure(ctx, wl, args.steps, args.warmup, args.blocks, args.profile_all,
+
+        def dump_outputs():
+            if rank == 0 and args.dump_outputs:
+                outputs.write(args.dump_outputs, wl.outputs())
+        # (--dump-outputs pins the number of blocks: the camera of the last timed frame must not depend on how fast the first block was)
+        times, prof, info = measure(ctx, wl, args.steps, args.warmup, args.blocks or (15 if args.dump_outputs else 0), args.profile_all,
                                     (lambda: dist.barrier()) if use_dist else None, reduce_max if use_dist else None,
-                                    agree if use_dist else None)
+                                    agree if use_dist else None, lean=not args.full, after_timed=dump_outputs)
 
     out = None
     if rank == 0:
         med = float(np.median(times))
         units = getattr(wl, "global_units", wl.units * world)
         live = None
-        if world == 1 and not args.no_live_traffic and os.environ.get("MI_BENCH_CHILD") != "1":
+        if args.full and world == 1 and not args.no_live_traffic and os.environ.get("MI_BENCH_CHILD") != "1":
             live = traffic.measure_live(traffic_args(workload, args), getattr(wl, "kernel_name", wl.dominant).split(" ")[0])
         out = {"metric": wl.metric, "value": round(units * args.steps / med, 1), "unit": wl.unit, "n_gpus": world, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": round(1e3 * med / args.steps, 5), "higher_is_better": True,
                "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": wl.config,
-               "timing": f"median of {len(times)} blocks of exactly {args.steps} steps, each between barrier + synchronize pairs, MAX over ranks per block",
+               "timing": (f"median of {len(times)} blocks of exactly {args.steps} steps, each between barrier + synchronize pairs, MAX over ranks per block"
+                          if args.full else f"one block of exactly {args.steps} steps between barrier + synchronize pairs, MAX over ranks"),
                "blocks": block_stats(np.array(times), args.steps), "roofline": roofline_of(wl, prof, args.steps, live), "cpu_baseline": None,
                "kernels": {k: round(v["avg_us"], 3) for k, v in prof.items() if v["launches"]}}
-        if getattr(wl, "frame_level_roofline", False):
+        if args.full and getattr(wl, "frame_level_roofline", False):
             out["roofline_frame"] = roofline_frame(wl, prof, args.steps, PROFILED_BLOCKS)
             out["roofline"] = reprice_per_frame(out["roofline"], out["roofline_frame"])
         if live:
@@ -236,7 +256,7 @@ def main():
         if scaling is None:
             del out["scaling"]  # one GPU makes no scaling claim
         out.update(info)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if workload == "frame":
                 out["cpu_baseline"] = cpu.cpu_baseline_frame(wl, args.cpu_seconds)
                 out["config0_cpu_plumbing"] = cpu.config0_cpu_plumbing(args.cpu_seconds)
@@ -246,11 +266,11 @@ def main():
                 out["cpu_baseline"] = cpu.cpu_baseline_tree_shape(wl, args.tree_shape_frame)
             else:
                 out["cpu_baseline"] = cpu.cpu_baseline_other(workload, wl)
-        if world == 1 and workload == "frame" and not args.no_end_to_end:
+        if args.full and world == 1 and workload == "frame" and not args.no_end_to_end:
             with torch.cuda.stream(stream):
                 out["end_to_end"] = e2e.end_to_end(ctx, wl, cpu_frame_ms=(out["cpu_baseline"] or {}).get("frame_ms"))
             out["end_to_end_host_layer"] = e2e.end_to_end_host_layer(wl.units)
-    if use_dist and workload == "sharded" and getattr(wl, "gather", None) is not None:
+    if args.full and use_dist and workload == "sharded" and getattr(wl, "gather", None) is not None:
         # The first N > 1 run has to certify more than speed: after the timed region every rank runs ONE more frame
         # with a known camera set, rank 0 fetches the GATHERED masks and compares them bit for bit with the masks of the same frame
         # computed over the whole scene in ONE context on its own GPU; the collective's own latency (events on the communication
@@ -287,7 +307,7 @@ def main():
             # what the driver's curve cannot show (its N = 1 point is the metric frame, another workload): this line's value against the
             # SAME scene on one GPU, per GPU
             out["scaling_efficiency"] = round(out["value"] / (world * single["value"]), 4)
-    if rank == 0 and world == 1 and workload == "frame" and not args.no_other_workloads:
+    if args.full and rank == 0 and world == 1 and workload == "frame" and not args.no_other_workloads:
         others = {}
         for name, builder in OTHER_WORKLOADS:
             c2 = api.Context(local_rank, stream.cuda_stream)

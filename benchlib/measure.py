@@ -8,9 +8,13 @@ import numpy as np
 from .common import HBM_PEAK_GBPS, PROFILED_BLOCKS, ROOT
 
 
-def measure(ctx, wl, steps, warmup, n_blocks=0, profile_all=False, barrier=None, reduce_max=None, agree=None, target_s=0.4):
+def measure(ctx, wl, steps, warmup, n_blocks=0, profile_all=False, barrier=None, reduce_max=None, agree=None, target_s=0.4,
+            lean=False, after_timed=None):
     """W untimed frames, then B blocks of exactly `steps` frames, each between barrier + synchronize pairs (MAX over ranks
-    per block), then PROFILED_BLOCKS blocks with per-dispatch events.  Returns (block seconds [B], per-kernel profile, info)."""
+    per block), then PROFILED_BLOCKS blocks with per-dispatch events.  Returns (block seconds [B], per-kernel profile, info).
+
+    lean: the W untimed frames, then ONE block -- `steps` timed frames in all -- and nothing else (no sizing block, no profiled
+    blocks: the profile comes back empty).  after_timed() is called once the last timed block has finished, before any profiled one."""
     import gc
     import torch
 
@@ -44,7 +48,10 @@ def measure(ctx, wl, steps, warmup, n_blocks=0, profile_all=False, barrier=None,
 
     if warmup:
         run_block(warmup)
-    est, _ = run_block(steps)                       # untimed: sizes the number of blocks
+    if lean:
+        n_blocks = 1
+    else:
+        est, _ = run_block(steps)                   # untimed: sizes the number of blocks
     if not n_blocks:
         n_blocks = int(min(600, max(15, target_s / max(est, 1e-6))))
         if agree:
@@ -65,18 +72,22 @@ def measure(ctx, wl, steps, warmup, n_blocks=0, profile_all=False, barrier=None,
         pass
     if reduce_max:
         times = reduce_max(times)
-    # profiled blocks: same frames, every launch of the workload's kernels timed (not part of the statistics)
-    ctx.profile_filter(None if profile_all else wl.kernels)
-    ctx.profile_sample(1)
-    ctx.profile_burst(0)
-    ctx.profile_enable(True)
-    prof_t = [run_block(steps)[0] for _ in range(PROFILED_BLOCKS)]
-    prof = ctx.profile_read()
-    ctx.profile_enable(False)
+    if after_timed:
+        after_timed()
+    info = {"host_enqueue_ms_per_step": round(1e3 * float(np.median(enq)) / steps, 5)}
+    prof = {}
+    if not lean:
+        # profiled blocks: same frames, every launch of the workload's kernels timed (not part of the statistics)
+        ctx.profile_filter(None if profile_all else wl.kernels)
+        ctx.profile_sample(1)
+        ctx.profile_burst(0)
+        ctx.profile_enable(True)
+        prof_t = [run_block(steps)[0] for _ in range(PROFILED_BLOCKS)]
+        prof = ctx.profile_read()
+        ctx.profile_enable(False)
+        info["profiled_blocks_ms_per_step"] = round(1e3 * float(np.median(prof_t)) / steps, 5)
     if gc_was_enabled:
         gc.enable()
-    info = {"host_enqueue_ms_per_step": round(1e3 * float(np.median(enq)) / steps, 5),
-            "profiled_blocks_ms_per_step": round(1e3 * float(np.median(prof_t)) / steps, 5)}
     if xt and xt["wait_ns"] > 0:
         # MI_EXCHANGE_PIPELINED paces the caller n_bufs - 1 frames ahead of the exchange: a device-bound frame shows up in the caller's
         # time as WAITING for a gathered buffer's previous all-gather, not as work.  host_busy = the enqueue time without that wait.

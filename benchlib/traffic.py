@@ -57,7 +57,7 @@ def measure_live(bench_args, kernel_prefix, budget_s=150.0):
             out_dir = os.path.join(tmp, ctr)
             cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", out_dir, "-o", "pmc", "--",
                    sys.executable, os.path.join(ROOT, "bench.py")] + list(bench_args) + \
-                  ["--steps", "10", "--warmup", "2", "--blocks", "2", "--no-cpu-baseline", "--no-other-workloads", "--no-end-to-end",
+                  ["--full", "--steps", "10", "--warmup", "2", "--blocks", "2", "--no-cpu-baseline", "--no-other-workloads", "--no-end-to-end",
                    "--no-live-traffic"]
             res = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=left)
             if res.returncode != 0:

@@ -66,6 +66,18 @@ def build_frame(ctx, args):
                   "entities/sec through propagate+cull+cluster at 1M entities", "entities/s", rows=n_rows,
                   kernels=["k_flat_propagate_cull", "k_compact_fast", "k_cluster_walk", "k_cluster_fill"])
     wl.scene, wl.first_light, wl.pos_range, wl.frusta0, wl.keep = sc, first_light, pr, frames[0].array, (views, keep)
+
+    def outputs():
+        """What a caller receives from the last frame that ran (--dump-outputs).  The lists' compaction that MI_CULL_MORE_FRAMES
+        deferred is enqueued by the download; every prepared view has the same 16x9x24 grid."""
+        off, idx, counts, far, total = ctx.cluster_download(views[0].n_clusters)
+        return {"global_transform": ctx.download_global_transforms(want_changed=False).reshape(-1, 12),
+                "view_visibility": ctx.download_view_visibility()[0],
+                "visibility_view0": ctx.download_visibility(0),
+                "visible_rows": ctx.download_visible_entities(0, 0)[1],
+                "cluster_offsets": off, "cluster_indices": idx, "cluster_counts": counts,
+                "cluster_farthest_z_and_total": np.array([far, total], np.float64)}
+    wl.outputs = outputs
     # "k_flat_propagate_cull" is the library's timer slot; the symbol rocprofv3 shows is the k_frame instantiation
     # <PROPAGATE, INLINE_VIEWS, WALK>: the cluster walk rides in the launch unless it runs as calls or a stream of its own
     wl.kernel_name = "k_frame<1,true,0>" if (separate or concurrent) else "k_frame<1,true,1>"

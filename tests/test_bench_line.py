@@ -152,6 +152,33 @@ def test_counter_csv_parsing(tmp_path):
     assert T.parse_counter_csv(str(p), "k_frame<1,true,true>", "WRITE_SIZE") == []
 
 
+def test_dump_outputs_writes_float_arrays_and_the_same_sample_every_time(tmp_path):
+    """benchlib.outputs.write (bench.py --dump-outputs): float32 / float64 .npy files, integers exact, a larger array cut to the same
+    seeded rows in every run, 64 MB at the most."""
+    import numpy as np
+    from benchlib import outputs as D
+    rows = D.MAX_ELEMS // 12 + 1000
+    g = np.arange(12 * rows, dtype=np.float32).reshape(rows, 12)
+    arrays = {"g": g, "bits": np.array([True, False, True]), "rows": np.array([0, (1 << 24) - 1], np.uint32),
+              "big_index": np.array([1 << 24, (1 << 31) + 1], np.uint32), "far_total": np.array([0.25, 7.0], np.float64)}
+    paths = D.write(str(tmp_path / "a"), arrays)
+    got = {k: np.load(p) for k, p in paths.items()}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in arrays)
+    assert got["bits"].dtype == np.float32 and got["bits"].tolist() == [1.0, 0.0, 1.0]
+    assert got["rows"].dtype == np.float32 and got["rows"].tolist() == [0.0, float((1 << 24) - 1)]
+    assert got["big_index"].dtype == np.float64 and got["big_index"].tolist() == [float(1 << 24), float((1 << 31) + 1)]
+    assert got["far_total"].dtype == np.float64 and got["far_total"].tolist() == [0.25, 7.0]
+    assert got["g"].dtype == np.float32 and got["g"].shape == (D.MAX_ELEMS // 12, 12)
+    picked = (got["g"][:, 0] / 12).astype(np.int64)                     # the rows the sample kept: ascending, each whole
+    assert (np.diff(picked) > 0).all() and np.array_equal(got["g"], g[picked])
+    again = np.load(D.write(str(tmp_path / "b"), {"g": g + 1.0})["g"])
+    assert np.array_equal(again, got["g"] + 1.0)                        # another run, the same rows
+    assert sum(os.path.getsize(p) for p in paths.values()) <= 64 * 1000 * 1000
+    import pytest
+    with pytest.raises(ValueError):
+        D.write(str(tmp_path / "c"), {f"g{i}": g for i in range(5)})    # 5 x 16 MB
+
+
 def test_bench_modules_keep_the_oracle_out_of_the_timed_path():
     """Only benchlib/cpu_baseline.py may import the oracle (the checker timed as a baseline)."""
     for name in os.listdir(os.path.join(ROOT, "benchlib")):

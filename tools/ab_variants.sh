@@ -7,7 +7,7 @@ mkdir -p $O; : > $O/summary.txt
 for r in $(seq 1 $ROUNDS); do
   for v in $VARS; do
     if [ "$v" = "-" ]; then unset MI_LIB_VARIANT; else export MI_LIB_VARIANT=$v; fi
-    timeout 300 python bench.py "$@" --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic > $O/${v}_$r.json 2> $O/${v}_$r.err
+    timeout 300 python bench.py "$@" --full --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic > $O/${v}_$r.json 2> $O/${v}_$r.err
     python - <<P >> $O/summary.txt
 import json
 try:

@@ -20,7 +20,7 @@ for s in large_tree deep_tree update_leaves update_shallow; do python tools/stri
 SHAPES="large_tree deep_tree update_leaves update_shallow humanoids_active wide_tree" WIDTHS="64 128" bash tools/strips_ab.sh $P/strips_ab > $P/strips_ab.md 2>&1
 bash tools/sharded_1rank.sh $P/sharded_1rank > $P/sharded_1rank.md 2>&1
 bash tools/profile.sh $TAG > $P/profile.log 2>&1
-timeout 1200 python bench.py > $P/bench_stdout.txt 2> $P/bench.err; echo "bench rc=$?" >> $P/bench.err
+timeout 1200 python bench.py --full > $P/bench_stdout.txt 2> $P/bench.err; echo "bench rc=$?" >> $P/bench.err
 tail -n 1 $P/bench_stdout.txt > $P/bench_line.json; cp bench_full.json $P/bench_full.json 2>/dev/null
 cp -r profiles/$TAG $P/profiles_$TAG 2>/dev/null
 cp profiles/rocprof_summary.json $P/rocprof_summary.json 2>/dev/null

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 O=${1:-gpurun_out/flat_pmc}
 ARGS=${2:---workload flat --entities 10000000 --views 4}
 mkdir -p $O
-COMMON="--steps 6 --warmup 2 --blocks 1 --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic"
+COMMON="--steps 6 --warmup 2 --blocks 1 --full --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic"
 for mv in ${3:-0 1}; do
   i=0
   for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" \

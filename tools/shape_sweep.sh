@@ -6,7 +6,7 @@ for shape in ${SHAPES:-large_tree wide_tree deep_tree chain ropes bundle update_
   for kind in all movers; do
     case $shape in tree_4ary*) [ $kind = movers ] && continue ;; esac
     timeout 300 python bench.py --workload tree --tree-shape $shape --tree-shape-frame $kind --steps 20 --warmup 5 --blocks 8 \
-        --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic --full-line 2> $OUT/${shape}_$kind.err | tail -n 2 | head -n 1 > $OUT/${shape}_$kind.json
+        --full --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic --full-line 2> $OUT/${shape}_$kind.err | tail -n 2 | head -n 1 > $OUT/${shape}_$kind.json
   done
 done
 python - "$OUT" <<'PY'

@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/sharded_1rank}
 mkdir -p $OUT
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MI_FORCE_DIST=1
-COMMON="--workload sharded --entities 1250000 --views 4 --steps 50 --warmup 10 --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic"
+COMMON="--workload sharded --entities 1250000 --views 4 --steps 50 --warmup 10 --full --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic"
 python bench.py $COMMON 2> $OUT/default_calibrated.err | tail -n 1 > $OUT/default_calibrated.json
 cp bench_full.json $OUT/default_calibrated_full.json
 MI_XCH_MODE=simple python bench.py $COMMON 2> $OUT/simple_async.err | tail -n 1 > $OUT/simple_async.json

@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/strips_ab}
 mkdir -p $OUT
 run() {  # name, shape, kind, tile mode
   timeout 300 python bench.py --workload tree --tree-shape $2 --tree-shape-frame $3 --tile-mode $4 --steps 50 --warmup 10 --blocks 8 \
-      --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic --full-line 2> $OUT/$1.err | tail -n 2 | head -n 1 > $OUT/$1.json
+      --full --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic --full-line 2> $OUT/$1.err | tail -n 2 | head -n 1 > $OUT/$1.json
 }
 for shape in ${SHAPES:-large_tree deep_tree update_leaves update_shallow humanoids_active humanoids_mixed wide_tree tree_4ary_depth11}; do
   for kind in all movers; do

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/tree_pmc
 mkdir -p $O
-COMMON="--workload tree --steps 10 --warmup 2 --blocks 2 --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic"
+COMMON="--workload tree --steps 10 --warmup 2 --blocks 2 --full --no-cpu-baseline --no-other-workloads --no-end-to-end --no-live-traffic"
 EXTRA=$2
 for m in $1; do
   i=0
