@@ -206,7 +206,7 @@ ABI_SYMBOLS = [
 # include/bevy_mi355x_debug.h: instrumentation and test hooks, exported by the same library, not part of the boundary
 DEBUG_SYMBOLS = [
     "mi_timer_begin", "mi_timer_end", "mi_profile_enable", "mi_profile_filter", "mi_profile_sample", "mi_profile_burst", "mi_profile_read",
-    "mi_profile_kernel_name", "mi_debug_set_tile_mode", "mi_debug_tree_trace", "mi_debug_tile_plan", "mi_debug_tile_groups", "mi_debug_strip_plan", "mi_debug_plan_strips", "mi_debug_exchange_times", "mi_debug_logf", "mi_debug_set_sphere_path", "mi_debug_set_row_summary", "mi_debug_set_tree_cull", "mi_debug_set_walk_inrow", "mi_debug_set_chunked_frames", "mi_debug_chunked_counts", "mi_debug_set_tile_pretest", "mi_debug_set_sorted_one_wg_limit", "mi_debug_set_static_cull_order", "mi_debug_static_cull_counts", "mi_debug_cluster_download_unjoined",
+    "mi_profile_kernel_name", "mi_debug_set_tile_mode", "mi_debug_tree_trace", "mi_debug_tile_plan", "mi_debug_tile_groups", "mi_debug_strip_plan", "mi_debug_plan_strips", "mi_debug_exchange_times", "mi_debug_logf", "mi_debug_set_sphere_path", "mi_debug_set_row_summary", "mi_debug_scale_summary_uniform_waves", "mi_debug_set_tree_cull", "mi_debug_set_walk_inrow", "mi_debug_set_chunked_frames", "mi_debug_chunked_counts", "mi_debug_set_tile_pretest", "mi_debug_set_sorted_one_wg_limit", "mi_debug_set_static_cull_order", "mi_debug_static_cull_counts", "mi_debug_cluster_download_unjoined",
 ]
 
 
@@ -983,6 +983,15 @@ class Context:
         """0 = 64 aligned rows that agree in Aabb / flags / RenderLayers read a 32-byte summary instead of their columns (default),
         1 = off (test / bench hook; results are identical)."""
         self._ck(self._lib.mi_debug_set_row_summary(self._h, int(mode)))
+
+    def debug_scale_summary_uniform_waves(self):
+        """Brings the row summary up to date and returns (waves whose rows share one Transform.scale bit for bit, each wave's flag as a
+        u8 array, summary launches that have carried the scale part so far).  (0, zeros, ...) with the summary switched off."""
+        n_waves = (self.n + 63) // 64
+        count, launches = C.c_uint32(0), C.c_uint32(0)
+        flags = np.zeros(max(n_waves, 1), np.uint8)
+        self._ck(self._lib.mi_debug_scale_summary_uniform_waves(self._h, C.byref(count), _ptr(flags, C.c_uint8), C.byref(launches)))
+        return count.value, flags[:n_waves], launches.value
 
     def debug_set_static_cull_order(self, mode):
         """0 = cull-only frames of a static scene run over the cell order from the second eligible frame on (default), 1 = never, 2 = at once, any row count, 3 = as 2 with the list kernels' runs capped at three (long runs, as beyond 16.7 M rows)."""

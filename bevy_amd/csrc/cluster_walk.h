@@ -162,7 +162,7 @@ __device__ __forceinline__ bool derive_row_visible(const ClusterObjects& o, cons
     V3 center = {}, half = {};
     bool summarised = false;
     if (o.row_summary && !o.derive_resident && !o.row_changed) {  // (uniform)
-        const uint4* p = reinterpret_cast<const uint4*>(o.row_summary) + 2ull * (row >> 6);
+        const uint4* p = reinterpret_cast<const uint4*>(o.row_summary) + (uint64_t)(ROWSUM_WORDS / 4u) * (row >> 6);
         const uint4 a = p[0], b = p[1];
         summarised = (b.w & (ROWSUM_UNIFORM_AABB | ROWSUM_UNIFORM_FLAGS)) == (ROWSUM_UNIFORM_AABB | ROWSUM_UNIFORM_FLAGS) && !(b.w & 0x04u);
         fl = b.w & 0xFFu;

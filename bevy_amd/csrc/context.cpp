@@ -234,7 +234,8 @@ Columns columns_of(mi_ctx* ctx) {
     c.g_changed_bits = ctx->g_chg_bits;
     c.vv_changed_bits = ctx->vv_chg_bits;
     c.changed_gen = ctx->changed_gen;
-    const bool rs_current = ctx->rs_lo[0] >= ctx->rs_hi[0] && ctx->rs_lo[1] >= ctx->rs_hi[1];
+    bool rs_current = true;
+    for (uint32_t p = 0; p < ROWSUM_PARTS; ++p) rs_current = rs_current && ctx->rs_lo[p] >= ctx->rs_hi[p];
     c.row_summary = (const uint32_t*)ctx->row_sum.p;
     c.row_summary_on = (ctx->row_sum_mode == 0 && ctx->row_sum.p && rs_current) ? 1u : 0u;
     return c;
@@ -242,10 +243,12 @@ Columns columns_of(mi_ctx* ctx) {
 
 void row_summary_touch(mi_ctx* ctx, uint32_t parts, uint32_t first_row, uint32_t n_rows) {
     if (n_rows == 0) return;
-    ctx->cells.valid = false;  // (the static cull order copies flags / RenderLayers / half extents per cell)
-    ctx->cells.quiet = 0;
+    if (parts & (ROWSUM_PART_AABB | ROWSUM_PART_FLAGS)) {
+        ctx->cells.valid = false;  // (the static cull order copies flags / RenderLayers / half extents per cell)
+        ctx->cells.quiet = 0;
+    }
     const uint32_t lo = first_row >> 6, hi = (uint32_t)(((uint64_t)first_row + n_rows + 63u) >> 6);
-    for (uint32_t p = 0; p < 2u; ++p) {
+    for (uint32_t p = 0; p < ROWSUM_PARTS; ++p) {
         if (!(parts & (1u << p))) continue;
         if (ctx->rs_lo[p] >= ctx->rs_hi[p]) {
             ctx->rs_lo[p] = lo;
@@ -265,24 +268,29 @@ int32_t row_summary_ensure(mi_ctx* ctx) {
         int32_t rc = ensure(ctx, ctx->row_sum, bytes);
         if (rc) return rc;
         HIP_TRY(ctx, hipMemsetAsync(ctx->row_sum.p, 0, ctx->row_sum.bytes, ctx->stream));
-        ctx->rs_lo[0] = ctx->rs_lo[1] = 0;
-        ctx->rs_hi[0] = ctx->rs_hi[1] = n_waves;
+        for (uint32_t p = 0; p < ROWSUM_PARTS; ++p) ctx->rs_lo[p] = 0, ctx->rs_hi[p] = n_waves;
     }
     if (ctx->row_sum_mode != 0) return MI_OK;  // (allocated all the same: the frame kernels' load of it is unconditional)
-    uint32_t lo[2], hi[2];
-    for (uint32_t p = 0; p < 2u; ++p) {
+    uint32_t lo[ROWSUM_PARTS], hi[ROWSUM_PARTS];
+    for (uint32_t p = 0; p < ROWSUM_PARTS; ++p) {
         lo[p] = std::min(ctx->rs_lo[p], n_waves);
         hi[p] = std::min(ctx->rs_hi[p], n_waves);
     }
     Columns c = columns_of(ctx);
     uint32_t* sum = (uint32_t*)ctx->row_sum.p;
-    if (lo[0] < hi[0] && lo[1] < hi[1] && lo[0] == lo[1] && hi[0] == hi[1]) {
-        HIP_TRY(ctx, launch_row_summary(c, lo[0], hi[0] - lo[0], ROWSUM_PART_AABB | ROWSUM_PART_FLAGS, sum, ctx->stream));
-    } else {
-        if (lo[0] < hi[0]) HIP_TRY(ctx, launch_row_summary(c, lo[0], hi[0] - lo[0], ROWSUM_PART_AABB, sum, ctx->stream));
-        if (lo[1] < hi[1]) HIP_TRY(ctx, launch_row_summary(c, lo[1], hi[1] - lo[1], ROWSUM_PART_FLAGS, sum, ctx->stream));
+    // one launch for the stale parts whose ranges coincide (a resize, the first frame), one each for the others
+    for (uint32_t p = 0; p < ROWSUM_PARTS; ++p) {
+        if (lo[p] >= hi[p]) continue;
+        uint32_t parts = 1u << p;
+        for (uint32_t q = p + 1u; q < ROWSUM_PARTS; ++q)
+            if (lo[q] == lo[p] && hi[q] == hi[p]) {
+                parts |= 1u << q;
+                lo[q] = hi[q] = 0;
+            }
+        HIP_TRY(ctx, launch_row_summary(c, lo[p], hi[p] - lo[p], parts, sum, ctx->stream));
+        if (parts & ROWSUM_PART_SCALE) ++ctx->n_scale_summary_launches;
     }
-    ctx->rs_lo[0] = ctx->rs_lo[1] = ctx->rs_hi[0] = ctx->rs_hi[1] = 0;
+    for (uint32_t p = 0; p < ROWSUM_PARTS; ++p) ctx->rs_lo[p] = ctx->rs_hi[p] = 0;
     return MI_OK;
 }
 
@@ -1111,7 +1119,7 @@ int32_t mi_columns_resize(mi_ctx* ctx, uint32_t n_rows) {
     if (n_rows != ctx->n) {
         ctx->sph_state = mi_ctx::SPH_INVALID;
         const uint32_t a = std::min(n_rows, ctx->n) & ~63u, b = std::max(n_rows, ctx->n);  // the wave the old end lies in and everything behind
-        row_summary_touch(ctx, ROWSUM_PART_AABB | ROWSUM_PART_FLAGS, a, b - a);
+        row_summary_touch(ctx, ROWSUM_PART_AABB | ROWSUM_PART_FLAGS | ROWSUM_PART_SCALE, a, b - a);
     }
     if (n_rows > ctx->n) {  // new rows are Added<GlobalTransform>: marked (a plain 1), uncounted
         ctx->changed_rows_hint = UINT64_MAX;
@@ -1239,11 +1247,13 @@ int32_t mi_upload_transforms(mi_ctx* ctx, uint32_t first_row, uint32_t n, const 
         HIP_TRY(ctx, hipHostGetDevicePointer(&dev, st, 0));
         if ((rc = cluster_join(ctx))) return rc;
         ctx->cl_inputs_dirty = true;
+        row_summary_touch(ctx, ROWSUM_PART_SCALE, first_row, n);
         HIP_TRY(ctx, launch_upload_trs((const float*)dev, ctx->t, ctx->r, ctx->s, first_row, n, ctx->stream));
         return MI_OK;
     }
     if ((rc = upload(ctx, ctx->t + 3 * (size_t)first_row, translation, (size_t)n * 12))) return rc;
     if ((rc = upload(ctx, ctx->r + 4 * (size_t)first_row, rotation, (size_t)n * 16))) return rc;
+    row_summary_touch(ctx, ROWSUM_PART_SCALE, first_row, n);
     if ((rc = upload(ctx, ctx->s + 3 * (size_t)first_row, scale, (size_t)n * 12))) return rc;
     return MI_OK;
 }
@@ -1290,6 +1300,14 @@ static int32_t scatter_indexed(mi_ctx* ctx, const uint32_t* rows, const float* t
     int32_t rc = cluster_join(ctx);
     if (rc) return rc;
     ctx->cl_inputs_dirty = true;
+    if (s) {  // the scale part of the row summary: a range that certainly covers the rows (a window without scale leaves it alone)
+        if (window_order != 0) {  // (strictly monotonic: the first and the last entry are the ends)
+            const uint32_t a = std::min(rows[0], rows[n - 1u]), b = std::max(rows[0], rows[n - 1u]);
+            row_summary_touch(ctx, ROWSUM_PART_SCALE, a, b - a + 1u);
+        } else {
+            row_summary_touch(ctx, ROWSUM_PART_SCALE, 0, ctx->n);
+        }
+    }
     // mark_dirty_trees for these rows in the same launch, when the frames run under the static-scene rule and the half the next
     // propagate will read holds nothing but such marks
     const bool mark_here = ctx->have_hierarchy && ctx->marks_live && ctx->tree_bytes && ctx->parent_idx.p &&
@@ -1469,6 +1487,7 @@ int32_t mi_commit_upload_window(mi_ctx* ctx, const mi_upload_window* w, uint32_t
                     if (w->rotation) HIP_TRY(ctx, hipMemcpyAsync(ctx->r + 4 * at, w->rotation + 4 * lo, cnt * 16, hipMemcpyHostToDevice, ctx->up_stream));
                     if (w->scale) HIP_TRY(ctx, hipMemcpyAsync(ctx->s + 3 * at, w->scale + 3 * lo, cnt * 12, hipMemcpyHostToDevice, ctx->up_stream));
                 }
+                if (w->scale) row_summary_touch(ctx, ROWSUM_PART_SCALE, (uint32_t)at, (uint32_t)cnt);
                 HIP_TRY(ctx, hipEventRecord(ctx->ev_up[ev], ctx->up_stream));
                 // the context's stream follows piece by piece: everything launched on it from here on sees the upload so far
                 HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_up[ev], 0));
@@ -1495,7 +1514,10 @@ int32_t mi_commit_upload_window(mi_ctx* ctx, const mi_upload_window* w, uint32_t
         // pinned -> device: three DMA copies straight from the window (no staging copy)
         if (w->translation) HIP_TRY(ctx, hipMemcpyAsync(ctx->t + 3 * (size_t)first_row, w->translation, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
         if (w->rotation) HIP_TRY(ctx, hipMemcpyAsync(ctx->r + 4 * (size_t)first_row, w->rotation, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-        if (w->scale) HIP_TRY(ctx, hipMemcpyAsync(ctx->s + 3 * (size_t)first_row, w->scale, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+        if (w->scale) {
+            row_summary_touch(ctx, ROWSUM_PART_SCALE, first_row, n);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->s + 3 * (size_t)first_row, w->scale, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+        }
         return MI_OK;
     }
     // (strictly monotonic rows -- a Changed<Transform> query over tables whose rows follow the Entity key, one way or the other -- are
@@ -2681,11 +2703,35 @@ int32_t mi_debug_set_tree_cull(mi_ctx* ctx, int32_t mode) {
     return MI_OK;
 }
 
-// test / bench hook: the per-wave summary of Aabb / flags / RenderLayers (RowSummary, kernels.h): 0 = in use (default), 1 = off
+// test / bench hook: the per-wave summary of Aabb / flags / RenderLayers / scale (RowSummary, kernels.h): 0 = in use (default), 1 = off
 int32_t mi_debug_set_row_summary(mi_ctx* ctx, int32_t mode) {
     ENTER(ctx);
     if (mode < 0 || mode > 1) return fail(ctx, MI_ERR_INVALID_ARG, "mi_debug_set_row_summary: mode %d", mode);
     ctx->row_sum_mode = mode;
+    return MI_OK;
+}
+
+// test hook: brings the row summary up to date (as a frame's entry does) and reports its scale part: how many waves are flagged
+// uniform, each wave's flag (out_flags: one byte per 64 rows, or NULL) and how many k_row_summary launches have carried the part so far.
+// With the summary switched off nothing is derived and no wave counts.
+int32_t mi_debug_scale_summary_uniform_waves(mi_ctx* ctx, uint32_t* out_count, uint8_t* out_flags, uint32_t* out_launches) {
+    ENTER(ctx);
+    const uint32_t n_waves = (uint32_t)words64(ctx->n);
+    uint32_t count = 0;
+    if (out_flags) memset(out_flags, 0, n_waves);
+    if (n_waves && ctx->row_sum_mode == 0) {
+        int32_t rc = row_summary_ensure(ctx);
+        if (rc) return rc;
+        std::vector<uint32_t> host((size_t)n_waves * ROWSUM_WORDS);
+        if ((rc = download(ctx, host.data(), ctx->row_sum.p, host.size() * 4))) return rc;
+        for (uint32_t w = 0; w < n_waves; ++w) {
+            const bool uniform = (host[(size_t)w * ROWSUM_WORDS + 7u] & ROWSUM_UNIFORM_SCALE) != 0u;
+            count += uniform ? 1u : 0u;
+            if (out_flags) out_flags[w] = uniform ? 1 : 0;
+        }
+    }
+    if (out_count) *out_count = count;
+    if (out_launches) *out_launches = ctx->n_scale_summary_launches;
     return MI_OK;
 }
 

@@ -214,11 +214,14 @@ struct mi_ctx {
 
     // ---- row summary (RowSummary, kernels.h): Aabb / flags / RenderLayers per 64 rows where they are uniform.  Derived from the
     // columns by k_row_summary; rs_lo / rs_hi = the waves [lo, hi) whose summary is out of date, per part (0 = Aabb, 1 = flags +
-    // layers).  The frame entry points bring it up to date first (row_summary_ensure); columns_of hands it to kernels only then.
+    // layers, 2 = Transform.scale).  The frame entry points bring it up to date first (row_summary_ensure); columns_of hands it to
+    // kernels only when every part is current.  Whatever writes a summarised column says so (row_summary_touch) -- an upload or
+    // window without scale does not touch part 2: a game that moves and turns its entities never re-derives it.
     DevBuf row_sum;
-    uint32_t rs_lo[2] = {0, 0}, rs_hi[2] = {0, 0};
+    uint32_t rs_lo[3] = {0, 0, 0}, rs_hi[3] = {0, 0, 0};
+    uint32_t n_scale_summary_launches = 0;  // k_row_summary launches that carried the scale part (mi_debug_scale_summary_uniform_waves)
     int32_t walk_inrow_mode = 0;  // mi_debug_set_walk_inrow: 0 = row-range bindings are walked by the frame kernel's own row workgroups, 1 = never
-    int32_t row_sum_mode = 0;  // mi_debug_set_row_summary: 0 = in use, 1 = off (every row reads its own Aabb / flags / layers)
+    int32_t row_sum_mode = 0;  // mi_debug_set_row_summary: 0 = in use, 1 = off (every row reads its own Aabb / flags / layers / scale)
 
     // ---- views / visibility ----
     DevBuf views;

@@ -91,20 +91,31 @@ struct Columns {
     uint64_t* g_changed_bits;   // ceil(n/64) words: GlobalTransform change tick bumped
     uint64_t* vv_changed_bits;  // ceil(n/64) words: ViewVisibility change tick bumped
     uint32_t changed_gen;       // the Transform change column holds STAMPS, see row_changed()
-    const uint32_t* row_summary;  // 8 words per 64 rows (RowSummary below); allocated whenever a frame kernel runs
+    const uint32_t* row_summary;  // ROWSUM_WORDS words per 64 rows (RowSummary below); allocated whenever a frame kernel runs
     uint32_t row_summary_on;      // 0 = out of date / switched off: every row reads its own columns
 };
 
 // Per 64 aligned rows, what the frame kernels would otherwise read per row although it rarely differs from row to row: Aabb (the
 // entities of a mesh are spawned together: one Aabb for all of them), the flags byte and the RenderLayers mask.  A wave fetches the
-// 32 bytes with scalar loads; where a bit says "uniform" its lanes take the values from there and issue no loads on the column:
+// first 32 bytes with scalar loads; where a bit says "uniform" its lanes take the values from there and issue no loads on the column:
 // 29 of the ~119 B a row of the all-dirty frame costs (24 Aabb + 1 flags + 4 layers).  Waves whose rows differ read the columns as
 // before.  (A wave counts as uniform in its RenderLayers only if none of its rows has a layer above 31: the summary holds one word.)
 // Written by k_row_summary from the columns themselves (after mi_upload_bounds / resize / visibility propagation, for the
 // waves they touched), so the columns stay the only source of truth.
-//   words 0-2 Aabb centre, 3-5 half extents (valid iff ROWSUM_UNIFORM_AABB), 6 RenderLayers mask, 7 = flags byte | ROWSUM_* bits
-constexpr uint32_t ROWSUM_WORDS = 8u, ROWSUM_UNIFORM_AABB = 0x80000000u, ROWSUM_UNIFORM_FLAGS = 0x40000000u;
-constexpr uint32_t ROWSUM_PART_AABB = 1u, ROWSUM_PART_FLAGS = 2u;
+//   words 0-2 Aabb centre, 3-5 half extents (valid iff ROWSUM_UNIFORM_AABB), 6 RenderLayers mask, 7 = flags byte | ROWSUM_* bits,
+//   8-10 Transform.scale of the wave's first row (valid iff ROWSUM_UNIFORM_SCALE), 11 spare (0)
+// The scale part: Transform.scale is one value across a spawn batch as a rule (Vec3::ONE more often than not), and the all-dirty
+// frame fetches its 12 B for every row.  ROWSUM_UNIFORM_SCALE says that every live row of the wave has the very bits of words 8-10
+// (-0.0 and +0.0 differ); the lanes of such a wave of a PROP == 1 frame kernel all read those 12 bytes -- one request per wave, at
+// an address chosen per wave, through the load instruction the other waves read their own rows with -- and issue no load on the
+// column: the same operations on the same values, the same bits.  (Taking the three words into scalar registers behind a wave-uniform
+// branch was the first form: it took k_frame<1, true, 1> from 20 to 52 bytes of scratch and from 18 to 25 spilled SGPRs, past what
+// tests/test_kernel_resources.py pins; the address select costs neither.)  Derived by k_row_summary like the other parts, for the
+// waves whose scale was written since -- every writer of the column says so (row_summary_touch) -- and an upload or window that
+// carries no scale leaves it alone.  The other readers of scale (PROP == 2's per-row reload, the hierarchy kernels, k_globals_ahead,
+// the cluster walk's derive mode) read the column.
+constexpr uint32_t ROWSUM_WORDS = 12u, ROWSUM_UNIFORM_AABB = 0x80000000u, ROWSUM_UNIFORM_FLAGS = 0x40000000u, ROWSUM_UNIFORM_SCALE = 0x20000000u;
+constexpr uint32_t ROWSUM_PART_AABB = 1u, ROWSUM_PART_FLAGS = 2u, ROWSUM_PART_SCALE = 4u, ROWSUM_PARTS = 3u;
 
 // The per-row Transform change byte: 0 = unchanged, 1 = changed (bulk uploads, rows never propagated), g in 2..255 = changed iff g is
 // the context's current generation -- what the indexed uploads write.  Consuming the column is then `generation += 1` on the host

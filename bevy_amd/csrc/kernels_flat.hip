@@ -52,7 +52,7 @@ __device__ __forceinline__ void st_affine(float* g, uint32_t row, const Affine& 
     p[2] = make_float4(a.m.z_axis.z, a.t.x, a.t.y, a.t.z);
 }
 
-// The wave's RowSummary (kernels.h): 32 bytes at a wave-uniform address, fetched with scalar loads.  bits = word 7, or 0 when the
+// The wave's RowSummary (kernels.h): its first 32 bytes at a wave-uniform address, fetched with scalar loads.  bits = word 7, or 0 when the
 // summary is not in use / the wave has no live row.
 struct RowSum {
     V3 center, half;
@@ -63,7 +63,7 @@ __device__ __forceinline__ RowSum load_row_summary(const Columns& c, uint32_t wa
     // valid -- row_summary is allocated whenever a frame kernel runs -- and what is not to be used is masked out of the bits
     const bool use = c.row_summary_on != 0u && wave_row0 < c.n;
     const uint32_t w = __builtin_amdgcn_readfirstlane(use ? wave_row0 >> 6 : 0u);
-    const uint4* p = reinterpret_cast<const uint4*>(c.row_summary) + 2ull * w;
+    const uint4* p = reinterpret_cast<const uint4*>(c.row_summary) + (uint64_t)(ROWSUM_WORDS / 4u) * w;
     const uint4 a = p[0], b = p[1];
     RowSum r;
     r.center = V3{__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z)};
@@ -265,6 +265,8 @@ __device__ __forceinline__ bool frame_riders(uint32_t n_tiles, const CompactFast
 // segment masks the VisibleEntities compaction consumes.
 // Algorithmic bytes per row, fused, V views: read 40 (T) + 24 (Aabb) + 1 (flags) + 4 (layers) + 1 (vv),
 // write 48 (G) + 1 (vv) + (V + 2 change masks) / 8 + V / 64 (wave counts).
+// Less what the wave's RowSummary (kernels.h) stands in for where its 64 rows agree: Aabb, flags and layers (29 B) in every variant,
+// and Transform.scale (12 B of the 40) where every row is propagated (PROP == 1) -- such a wave reads 48 B of summary instead.
 // ---------------------------------------------------------------------------------------------
 // WALK: 0 = none; 1 = the launch may carry this frame's light-cluster walk; 2 = ... and there are spot lights among the objects (the
 // walk then also runs the cone test against the clusters' bounding spheres, assign.rs:681-738: five more registers per object, so
@@ -342,9 +344,12 @@ __device__ __forceinline__ void frame_workgroup(const Columns& c, const ViewSet&
     V3 t_in = {}, s_in = {};
     V4 q_in = {};
     if (PROPAGATE && live) {
+        // scale: where the wave's rows share one (ROWSUM_UNIFORM_SCALE, wave-uniform) every lane reads the summary's copy -- one 12-byte
+        // request per wave, none on the column -- through the same load instruction the other waves read their own rows with
+        const bool uni_s = (rs.bits & ROWSUM_UNIFORM_SCALE) != 0u;
+        const float* sp3 = uni_s ? reinterpret_cast<const float*>(c.row_summary) + (uint64_t)ROWSUM_WORDS * (wave_row0 >> 6) + 8u : c.scale + 3ull * row;
         if (fl_frame & CULL_NT_LOADS) {  // (launch-uniform: a big context, kernels.h)
             const float* tp = c.translation + 3ull * row;
-            const float* sp3 = c.scale + 3ull * row;
             const v4f qv = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(c.rotation) + row);
             t_in = V3{__builtin_nontemporal_load(tp), __builtin_nontemporal_load(tp + 1), __builtin_nontemporal_load(tp + 2)};
             q_in = V4{qv.x, qv.y, qv.z, qv.w};
@@ -352,7 +357,7 @@ __device__ __forceinline__ void frame_workgroup(const Columns& c, const ViewSet&
         } else {
             t_in = ld3(c.translation, row);
             q_in = ld4(c.rotation, row);
-            s_in = ld3(c.scale, row);
+            s_in = ld3(sp3, 0);
         }
     }
     if (live) {
@@ -1226,7 +1231,7 @@ hipError_t launch_globals_ahead(const float* t, const float* r, const float* s, 
 // reset_view_visibility: bits = (bits & 1) << 1 for rows without NoCpuCulling; clears the change mask.
 // RowSummary (kernels.h) of the waves first_wave .. first_wave + n_waves - 1, from the columns: a wave per 64 rows compares every
 // live row's bits with its first row's.  parts: ROWSUM_PART_AABB rewrites words 0-5 and the Aabb bit, ROWSUM_PART_FLAGS words 6-7's
-// flags / layers and their bit (the other part of word 7 is kept).
+// flags / layers and their bit, ROWSUM_PART_SCALE words 8-10 and the scale bit (the other parts' share of word 7 is kept).
 __global__ void __launch_bounds__(256) k_row_summary(Columns c, uint32_t first_wave, uint32_t n_waves, uint32_t parts, uint32_t* __restrict__ summary) {
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (w >= n_waves) return;
@@ -1257,7 +1262,17 @@ __global__ void __launch_bounds__(256) k_row_summary(Columns c, uint32_t first_w
         bits = (bits & ~(ROWSUM_UNIFORM_FLAGS | 0xFFu)) | (uniform ? ROWSUM_UNIFORM_FLAGS : 0u) | (fl0 & 0xFFu);
         if (lane == 0u) o[6] = lm0;
     }
-    if (lane == 0u) o[7] = bits & (ROWSUM_UNIFORM_AABB | ROWSUM_UNIFORM_FLAGS | 0xFFu);
+    if (parts & ROWSUM_PART_SCALE) {
+        const F3 sc = reinterpret_cast<const F3*>(c.scale)[rrow];
+        const uint32_t v[3] = {__float_as_uint(sc.x), __float_as_uint(sc.y), __float_as_uint(sc.z)};
+        bool same = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) same = same && v[k] == (uint32_t)__builtin_amdgcn_readfirstlane((int)v[k]);
+        const bool uniform = __ballot(!same) == 0ull;
+        bits = (bits & ~ROWSUM_UNIFORM_SCALE) | (uniform ? ROWSUM_UNIFORM_SCALE : 0u);
+        if (lane == 0u) reinterpret_cast<uint4*>(o)[2] = make_uint4(v[0], v[1], v[2], 0u);
+    }
+    if (lane == 0u) o[7] = bits & (ROWSUM_UNIFORM_AABB | ROWSUM_UNIFORM_FLAGS | ROWSUM_UNIFORM_SCALE | 0xFFu);
 }
 
 __global__ void __launch_bounds__(256) k_vis_begin(Columns c) {

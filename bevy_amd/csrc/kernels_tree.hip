@@ -442,7 +442,7 @@ __device__ __forceinline__ void tile_cull_rows(const Columns& c, const TreeCull&
     const uint32_t vv0 = c.view_visibility[rrow];
     // Aabb / flags / RenderLayers: the 64-row summary where it says the rows agree (per lane: a wave's rows span two summaries or,
     // for the upper rows, several), else the columns
-    const uint4* sp = reinterpret_cast<const uint4*>(c.row_summary) + 2ull * (c.row_summary_on ? rrow >> 6 : 0u);
+    const uint4* sp = reinterpret_cast<const uint4*>(c.row_summary) + (uint64_t)(ROWSUM_WORDS / 4u) * (c.row_summary_on ? rrow >> 6 : 0u);
     const uint4 sa = sp[0], sb = sp[1];
     const uint32_t bits = c.row_summary_on ? sb.w : 0u;
     uint32_t fl = bits & 0xFFu, emask = sb.z, emask_hi = 0u;

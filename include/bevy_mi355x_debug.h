@@ -81,9 +81,14 @@ int32_t mi_debug_set_walk_inrow(mi_ctx* ctx, int32_t mode);
  * view and nothing else needs the frame kernels (default: measured faster there), 1 = always tile launch + cull launch,
  * 2 = fused whenever it applies.  Results are identical. */
 int32_t mi_debug_set_tree_cull(mi_ctx* ctx, int32_t mode);
-/* The per-wave summary of Aabb / flags / RenderLayers (64 aligned rows that agree read 32 bytes instead of 64 x 29): 0 = in use
+/* The per-wave summary of Aabb / flags / RenderLayers (64 aligned rows that agree read 32 bytes instead of 64 x 29) and scale: 0 = in use
  * (default), 1 = off -- every row reads its own columns.  Results are identical; A/B timing and tests. */
 int32_t mi_debug_set_row_summary(mi_ctx* ctx, int32_t mode);
+/* The summary's scale part (64 aligned rows whose Transform.scale agrees bit for bit take it from 12 bytes instead of 64 x 12 in the
+ * all-rows frame; switched off with the rest by mi_debug_set_row_summary(1)).  Brings the summary up to date as a frame's entry
+ * would, then: *out_count = waves flagged uniform, out_flags[ceil(n / 64)] = each wave's flag (or NULL), *out_launches = summary
+ * launches that have carried the part since the context was created (tests: a window without scale must not cause one). */
+int32_t mi_debug_scale_summary_uniform_waves(mi_ctx* ctx, uint32_t* out_count, uint8_t* out_flags, uint32_t* out_launches);
 
 /* The world-sphere path of the cull-only and changed-rows frames (kernels_flat.hip, k_frame_sph): 0 = used from the second frame in
  * a row that rewrites no or few GlobalTransforms (default), 1 = never, 2 = at once (the first such frame rebuilds the column). */
