@@ -200,7 +200,7 @@ ABI_SYMBOLS = [
     "mi_cluster_config_default", "mi_cluster_config_resolve", "mi_cluster_sort_truncate", "mi_cluster_bind_objects_to_rows", "mi_cluster_bind_objects_to_row_list",
     "mi_cluster_assign_frame",
     "mi_batch_upload_rows", "mi_batch_upload_sets", "mi_batch_upload_row_bins", "mi_batch_upload_bins", "mi_batch_build", "mi_batch_build_phase",
-    "mi_batch_sorted_build", "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
+    "mi_batch_sorted_build", "mi_upload_depth_bias", "mi_phase_sort", "mi_phase_sort_download", "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
     "mi_bind_visibility_output", "mi_exchange_set_mode", "mi_exchange_configure", "mi_exchange_configure_multi", "mi_exchange_configure_owned", "mi_exchange_group_flush", "mi_exchange_last", "mi_exchange_download", "mi_device_buffer",
 ]
 # include/bevy_mi355x_debug.h: instrumentation and test hooks, exported by the same library, not part of the boundary
@@ -797,6 +797,25 @@ class Context:
         flags = (SORTED_AUTOMATIC_BATCHING if automatic_batching else 0) | (SORTED_NO_INDIRECT_DRAWING if no_indirect_drawing else 0) \
             | (SORTED_NO_GPU_PREPROCESSING if no_gpu_preprocessing else 0)
         self._ck(self._lib.mi_batch_sorted_build(self._h, len(it), it.ctypes.data_as(C.c_void_p) if len(it) else None, ini, C.c_uint32(flags)))
+
+    def upload_depth_bias(self, depth_bias, first_row=0):
+        """The material depth_bias of the rows (0.0 where never uploaded): added to the view distance by phase_sort."""
+        b = _f32(depth_bias)
+        self._ck(self._lib.mi_upload_depth_bias(self._h, first_row, len(b), _ptr(b, C.c_float)))
+
+    def phase_sort(self, view, class_bit, row2):
+        """sort_phase_system for (view, class_bit): -> dict(rows, entity_keys, distance) of the VisibleEntities list ordered by
+        dot4(row2, (translation, 1)) + depth_bias, ascending and stable.  row2 = row 2 of view_from_world."""
+        r2 = np.ascontiguousarray(row2, np.float32).reshape(4)
+        self._ck(self._lib.mi_phase_sort(self._h, int(view), int(class_bit), _ptr(r2, C.c_float), 0))
+        cnt = C.c_uint32(0)
+        rc = self._lib.mi_phase_sort_download(self._h, None, None, None, 0, C.byref(cnt))
+        if rc not in (MI_OK, MI_ERR_CAPACITY):
+            self._ck(rc)
+        m = cnt.value
+        rows, keys, dist = np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.float32)
+        self._ck(self._lib.mi_phase_sort_download(self._h, _ptr(rows, C.c_uint32), _ptr(keys, C.c_uint64), _ptr(dist, C.c_float), m, C.byref(cnt)))
+        return dict(rows=rows[:m], entity_keys=keys[:m], distance=dist[:m])
 
     def batch_download(self):
         """-> dict: work_items / metadata / batch_sets (lists indexed by mesh class, u32 arrays), records u32[k, 8], unbatchable

@@ -1016,7 +1016,7 @@ int32_t mi_ctx_destroy(mi_ctx* ctx) {
     void* cols[] = {ctx->t, ctx->r, ctx->s, ctx->g, ctx->c, ctx->h, ctx->flags, ctx->vv, ctx->changed, ctx->g_changed_bytes,
                     ctx->layers, ctx->layers_hi, ctx->class_mask, ctx->keys, ctx->g_chg_bits, ctx->vv_chg_bits, ctx->vv_chg_alt, ctx->tree_bytes,
                     ctx->range, ctx->visibility, ctx->inh_changed, ctx->bt_set, ctx->bt_bin, ctx->bt_input, ctx->bt_row_meta,
-                    ctx->bt_kind, ctx->bt_cpu_bin, ctx->bt_bucket};
+                    ctx->bt_kind, ctx->bt_cpu_bin, ctx->bt_bucket, ctx->depth_bias};
     for (void* p : cols)
         if (p) hipFree(p);
     DevBuf* bufs[] = {&ctx->sph, &ctx->row_sum, &ctx->anc, &ctx->order, &ctx->chains, &ctx->snap, &ctx->tree_trace, &ctx->inh_bits, &ctx->sparse_cnt, &ctx->sparse_rows, &ctx->sparse_total, &ctx->sparse_g, &ctx->g_pre, &ctx->parent_idx, &ctx->node_flags, &ctx->tiles, &ctx->wtiles, &ctx->strips, &ctx->strip_rounds, &ctx->level_offs_dev, &ctx->views,
@@ -1027,7 +1027,8 @@ int32_t mi_ctx_destroy(mi_ctx* ctx) {
                       &ctx->bt_md[1], &ctx->bt_bs[0], &ctx->bt_bs[1], &ctx->bt_records, &ctx->bt_totals, &ctx->bt_bucket_desc, &ctx->bt_meta_out,
                       &ctx->bt_inst[0], &ctx->bt_inst[1], &ctx->bt_plan, &ctx->bt_unb, &ctx->bt_items, &ctx->bt_batches, &ctx->bt_sorted_partials,
                       &ctx->cl_row_list, &ctx->cl_remap, &ctx->cl_bind_oc, &ctx->cl_bind_idx, &ctx->cl_block_counts, &ctx->cl_pair_cb, &ctx->cl_pair_mask, &ctx->cl_acc,
-                      &ctx->cl_offsets, &ctx->cl_indices, &ctx->cl_scalars};
+                      &ctx->cl_offsets, &ctx->cl_indices, &ctx->cl_scalars, &ctx->ps_pairs[0], &ctx->ps_pairs[1], &ctx->ps_table, &ctx->ps_rows,
+                      &ctx->ps_keys, &ctx->ps_dist, &ctx->ps_count};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& sl : ctx->cl_parked)  // (the parked cluster views' buffers; the selected one's are in the list above)
@@ -1157,6 +1158,7 @@ int32_t mi_columns_resize(mi_ctx* ctx, uint32_t n_rows) {
         if ((rc = grow_column(ctx, ctx->bt_kind, 1, old, new_cap, 0))) return rc;  // MI_BATCH_ROW_MULTIDRAWABLE
         if ((rc = grow_column(ctx, ctx->bt_cpu_bin, 1, old, new_cap, 0))) return rc;
         if ((rc = grow_column(ctx, ctx->bt_bucket, 1, old, new_cap, 0xFF))) return rc;
+        if (ctx->depth_bias && (rc = grow_column(ctx, ctx->depth_bias, 1, old, new_cap, 0))) return rc;
         // default RenderLayers = layer 0 (mask 1) for rows never uploaded
         {
             std::vector<uint32_t> ones(new_cap - old, 1u);
@@ -1204,7 +1206,7 @@ int32_t mi_columns_resize(mi_ctx* ctx, uint32_t n_rows) {
             {ctx->flags, 1, MI_FLAG_INHERITED_VISIBLE}, {ctx->vv, 1, 0}, {ctx->changed, 1, 1}, {ctx->g_changed_bytes, 1, 0},
             {ctx->layers_hi, 4, 0}, {ctx->class_mask, 4, 0}, {ctx->keys, 8, 0}, {ctx->range, 8, 0}, {ctx->visibility, 1, 0}, {ctx->inh_changed, 1, 0},
             {ctx->bt_set, 4, 0xFF}, {ctx->bt_bin, 4, 0}, {ctx->bt_input, 4, 0}, {ctx->bt_row_meta, 4, 0xFF},
-            {ctx->bt_kind, 1, 0}, {ctx->bt_cpu_bin, 4, 0}, {ctx->bt_bucket, 4, 0xFF}};
+            {ctx->bt_kind, 1, 0}, {ctx->bt_cpu_bin, 4, 0}, {ctx->bt_bucket, 4, 0xFF}, {ctx->depth_bias, 4, 0}};
         for (auto& cdesc : cols)
             if (cdesc.p) HIP_TRY(ctx, hipMemsetAsync((char*)cdesc.p + (size_t)lo * cdesc.elem, cdesc.fill, (size_t)cnt * cdesc.elem, ctx->stream));
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->layers + lo), 1, cnt, ctx->stream));  // default RenderLayers = layer 0

@@ -1,5 +1,5 @@
 // ctx.h -- internal to the library: the context object behind the opaque mi_ctx handle and the helpers the
-// entry-point files (context.cpp, ctx_hierarchy.cpp, ctx_exchange.cpp, ctx_batch.cpp, ctx_cluster.cpp) share.
+// entry-point files (context.cpp, ctx_hierarchy.cpp, ctx_exchange.cpp, ctx_batch.cpp, ctx_phase_sort.cpp, ctx_cluster.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -350,6 +350,12 @@ struct mi_ctx {
         bt_counters, bt_wi[2], bt_md[2], bt_bs[2], bt_records, bt_totals;
     uint32_t bt_n_sets = 0, bt_n_meta = 0;
     bool bt_have_rows = false, bt_have_sets = false, bt_built = false;
+    // sort_phase_system (ctx_phase_sort.cpp, kernels_phase_sort.hip)
+    float* depth_bias = nullptr;  // per-row column: allocated by the first mi_upload_depth_bias (nullptr = every bias is 0.0f)
+    DevBuf ps_pairs[2], ps_table, ps_rows, ps_keys, ps_dist, ps_count;
+    enum PsState : uint32_t { PS_NONE = 0, PS_SORTED = 1, PS_EMPTY = 2 };  // what mi_phase_sort_download hands out
+    uint32_t ps_state = PS_NONE;
+    bool ps_lds_set = false;      // the kernels' dynamic LDS limit has been raised
     DevBuf cl_remap, cl_bind_oc, cl_bind_idx, cl_block_counts, cl_pair_cb, cl_pair_mask, cl_acc, cl_offsets, cl_indices, cl_scalars;
     // derive mode of an assignment that runs in or next to the frame kernel: which rows that frame's propagate writes (cull_frame sets them)
     const uint8_t* cl_derive_changed = nullptr;

@@ -792,4 +792,34 @@ uint32_t batch_sorted_partial_words(uint32_t n_items);
 hipError_t launch_batch_sorted(const SortedArgs& a, hipStream_t stream, void (*mark)(void*, uint32_t), void* mark_ctx, uint32_t* partials = nullptr,
                                uint32_t one_wg_limit = SORTED_ONE_WG_ITEMS);
 
+// ---- sort_phase_system (kernels_phase_sort.hip) -------------------------------------------------
+// Orders one VisibleEntities list by view distance: a stable LSD radix sort of (key, row) pairs, 8-bit digits, 4 passes.  The key is
+// the distance's bits mapped to an unsigned order (negative: all bits flipped, otherwise: the sign bit), the pair one 64-bit word
+// (key << 32 | row).  The length of the list is a device value: the launches are sized by the capacity `n` and read the count.
+//   up to PS_ONE_WG_MAX items: k_phase_sort_one -- one workgroup of 1024 threads keeps the pairs in registers and one LDS array
+//     through all four passes and writes the outputs once;
+//   longer: k_phase_keys, then per pass k_ps_hist / k_ps_scan / k_ps_scatter over tiles of PS_ONE_WG_MAX items; the last scatter
+//     writes the outputs.  No workgroup waits for another: the launch boundaries are the only ordering.
+// Both forms are enqueued when n > PS_ONE_WG_MAX (the count decides on the device which one does anything).
+constexpr uint32_t PS_ONE_WG_MAX = 8192;
+constexpr uint32_t PS_DIGITS = 256;
+struct PhaseSortArgs {
+    uint32_t n;                   // rows of the context: the capacity of the list and of every buffer below
+    const uint32_t* list;         // the (view, class) list of rows, in Entity order
+    const uint64_t* list_base;    // nullptr, or where the list starts in `list` (the general compaction's segment bases)
+    const uint32_t* list_count;   // its length (device)
+    const float* global;          // 12 floats per row: the translation is floats 9..11
+    const float* depth_bias;      // per row, or nullptr = 0.0f
+    const uint64_t* entity_keys;  // per row, or nullptr = the row number
+    float row2[4];                // row 2 of view_from_world
+    uint64_t* pairs[2];           // [ceil(n / PS_ONE_WG_MAX) * PS_ONE_WG_MAX] each; unused (nullptr) when n <= PS_ONE_WG_MAX
+    uint32_t* table;              // [PS_DIGITS][tiles]: per-tile digit counts, then their digit-major exclusive scan
+    uint32_t* out_rows;           // [n]
+    uint64_t* out_keys;           // [n]
+    float* out_distance;          // [n]
+    uint32_t* out_count;          // [1]
+};
+hipError_t set_phase_sort_lds_limit();  // once per process and device, before the first launch_phase_sort
+hipError_t launch_phase_sort(const PhaseSortArgs& a, hipStream_t stream);
+
 }  // namespace mi

@@ -773,6 +773,35 @@ typedef struct mi_sorted_batch {
 #define MI_SORTED_NO_GPU_PREPROCESSING 0x4u
 int32_t mi_batch_sorted_build(mi_ctx* ctx, uint32_t n_items, const mi_sorted_item* items, const mi_batch_initial* initial, uint32_t flags);
 
+/* The order of a sorted phase: render_phase's sort_phase_system for one (view, class), on the device.  What the reference does per
+ * view and visible item -- distance = ViewRangefinder3d::distance_translation(translation) + depth_bias, then
+ * radsort::sort_by_key(items, |i| i.distance), stable and ascending -- runs over the VisibleEntities list the last cull left in
+ * device memory and the GlobalTransform column: nothing is downloaded, sorted on a core and uploaded again.
+ *   mi_upload_depth_bias    optional per-row column (the material's depth_bias), 0.0f for rows never uploaded; 4 bytes per row,
+ *                           allocated by the first upload.
+ *   mi_phase_sort           orders the list of (view, class_bit) by
+ *                             dot4(view_from_world_row2, (G.translation, 1)) + depth_bias[row]
+ *                           ascending; ties keep the list's Entity order.  dot4 is glam's Vec4::dot as the library states it
+ *                           everywhere, (x x' + z z') + (y y' + w w'), every operation rounded on its own, then one f32 add of the
+ *                           bias.  Preconditions as mi_batch_build_phase: MI_ERR_NOT_READY before a cull, MI_ERR_INVALID_ARG for a
+ *                           view the last cull did not have or for any flag (none is defined: pass 0); a class no row carries is an
+ *                           empty phase.  Asynchronous: the length of the list is never read on the host.
+ *   mi_phase_sort_download  the phase of the last mi_phase_sort: rows, their entity keys (the row number without
+ *                           mi_upload_entity_keys) and their distances, any of them NULL; *out_count is always set,
+ *                           MI_ERR_CAPACITY if it exceeds `capacity` (as mi_download_visible_entities).
+ * Order of special values: items compare by the distance's bits mapped to an unsigned key, bits ^ (bits >> 31 ? 0xFFFFFFFF :
+ * 0x80000000): -inf < negatives < -0 < +0 < positives < +inf, a NaN before or behind all of them by its sign bit.  The NaN
+ * placement follows from that mapping (radsort's own for f32); it has not been pinned against a run of the reference.
+ * Cost: lists of up to 8192 items are one launch of one workgroup; longer ones take 14 short launches (whenever the context has
+ * more than 8192 rows both forms are enqueued and the count decides on the device which one works).  Measured with the download
+ * against download + numpy on the host (profiles/r08_phase_sort/ab.md): 4096 items 114 us against 173, 65536 items 0.6 ms against
+ * 3.9, 1 M items 1.3 ms against 81.  Phases shorter than 4096 items have not been measured: there the call is launch and fetch
+ * latency (~0.1 ms), which a core may well beat. */
+int32_t mi_upload_depth_bias(mi_ctx* ctx, uint32_t first_row, uint32_t n, const float* depth_bias);
+int32_t mi_phase_sort(mi_ctx* ctx, uint32_t view, uint32_t class_bit, const float view_from_world_row2[4], uint32_t flags);
+int32_t mi_phase_sort_download(mi_ctx* ctx, uint32_t* out_rows, uint64_t* out_entity_keys, float* out_distance, uint32_t capacity,
+                               uint32_t* out_count);
+
 /* ======================================================================================= */
 /* camera helpers (pure host code; what update_frusta computes, visibility/mod.rs:627-636)   */
 /* ======================================================================================= */
