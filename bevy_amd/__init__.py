@@ -47,3 +47,4 @@ CULL_STATIC_OPT = 0x40  # mi_propagate_and_cull with a hierarchy: StaticTransfor
 PROPAGATE_ALL_DIRTY = 0x1
 PROPAGATE_STATIC_OPT = 0x2
 NO_PARENT = 0xFFFFFFFF
+SKIN_NO_JOINT = 0xFFFFFFFF  # MI_SKIN_NO_JOINT: a joint slot without a row

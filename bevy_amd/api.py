@@ -184,6 +184,10 @@ BATCH_ROW_MULTIDRAWABLE, BATCH_ROW_BATCHABLE, BATCH_ROW_UNBATCHABLE, BATCH_ROW_N
 BATCH_NO_INDIRECT_DRAWING = 0x1
 SORTED_AUTOMATIC_BATCHING, SORTED_NO_INDIRECT_DRAWING, SORTED_NO_GPU_PREPROCESSING = 0x1, 0x2, 0x4
 NO_INPUT_INDEX = 0xFFFFFFFF
+SKIN_NO_JOINT = 0xFFFFFFFF
+SKIN_MATRICES, SKIN_BOUNDS, SKIN_KEEP_PREVIOUS = 0x1, 0x2, 0x4
+BUF_JOINT_MATRICES, BUF_JOINT_MATRICES_PREVIOUS = 12, 13  # device_buffer(which)
+JOINT_AABB_DTYPE = np.dtype([("joint", np.uint32), ("center", np.float32, 3), ("half_extents", np.float32, 3)])  # mi_joint_aabb
 
 ABI_SYMBOLS = [
     "mi_abi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_last_error_string", "mi_synchronize",
@@ -200,7 +204,8 @@ ABI_SYMBOLS = [
     "mi_cluster_config_default", "mi_cluster_config_resolve", "mi_cluster_sort_truncate", "mi_cluster_bind_objects_to_rows", "mi_cluster_bind_objects_to_row_list",
     "mi_cluster_assign_frame",
     "mi_batch_upload_rows", "mi_batch_upload_sets", "mi_batch_upload_row_bins", "mi_batch_upload_bins", "mi_batch_build", "mi_batch_build_phase",
-    "mi_batch_sorted_build", "mi_upload_depth_bias", "mi_phase_sort", "mi_phase_sort_download", "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
+    "mi_batch_sorted_build", "mi_upload_depth_bias", "mi_phase_sort", "mi_phase_sort_download", "mi_skin_upload_inverse_bindposes", "mi_skin_upload", "mi_skin_frame", "mi_skin_download_matrices", "mi_skin_download_bounds",
+    "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
     "mi_bind_visibility_output", "mi_exchange_set_mode", "mi_exchange_configure", "mi_exchange_configure_multi", "mi_exchange_configure_owned", "mi_exchange_group_flush", "mi_exchange_last", "mi_exchange_download", "mi_device_buffer",
 ]
 # include/bevy_mi355x_debug.h: instrumentation and test hooks, exported by the same library, not part of the boundary
@@ -407,6 +412,7 @@ class Context:
             raise MiError(rc, msg)
         self.n = 0
         self.n_views = 0
+        self._n_skins = self._n_slots = 0
         # test harness only: run a whole test session under one tile kernel (the library itself reads no environment)
         if os.environ.get("MI_TEST_TILE_MODE"):
             self.debug_set_tile_mode(int(os.environ["MI_TEST_TILE_MODE"]))
@@ -816,6 +822,45 @@ class Context:
         rows, keys, dist = np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.float32)
         self._ck(self._lib.mi_phase_sort_download(self._h, _ptr(rows, C.c_uint32), _ptr(keys, C.c_uint64), _ptr(dist, C.c_float), m, C.byref(cnt)))
         return dict(rows=rows[:m], entity_keys=keys[:m], distance=dist[:m])
+
+    # skinned meshes
+    def upload_inverse_bindposes(self, mat4, first=0):
+        """Matrices [first, first + n) of the pool of inverse bindposes: f32[n, 16] (or [n, 4, 4] as [column][row]), column-major."""
+        m = _f32(mat4).reshape(-1)
+        self._ck(self._lib.mi_skin_upload_inverse_bindposes(self._h, int(first), len(m) // 16, _ptr(m, C.c_float)))
+
+    def upload_skins(self, skins, joint_rows, aabb_joint=None, aabb_center=None, aabb_half=None):
+        """skins: u32[n, 6] = (mesh_row, first_joint, n_joints, first_bindpose, first_aabb, n_aabbs) per skin (mi_skin); joint_rows:
+        u32[n_slots], SKIN_NO_JOINT where a joint has no row; the joint AABBs as three arrays: joint index within the skin u32[k],
+        centre f32[k, 3], half extents f32[k, 3]."""
+        sk = _u32(skins).reshape(-1, 6)
+        jr = _u32(joint_rows).reshape(-1)
+        k = 0 if aabb_joint is None else len(aabb_joint)
+        ab = np.zeros(k, JOINT_AABB_DTYPE)
+        if k:
+            ab["joint"], ab["center"], ab["half_extents"] = aabb_joint, np.reshape(aabb_center, (k, 3)), np.reshape(aabb_half, (k, 3))
+        self._ck(self._lib.mi_skin_upload(self._h, len(sk), sk.ctypes.data_as(C.c_void_p) if len(sk) else None, len(jr),
+                                          _ptr(jr, C.c_uint32) if len(jr) else None, k, ab.ctypes.data_as(C.c_void_p) if k else None))
+        self._n_skins, self._n_slots = len(sk), len(jr)
+
+    def skin_frame(self, matrices=True, bounds=True, keep_previous=False):
+        """Between propagate and cull: the joint matrices of every slot and / or the refitted Aabb of every skin with joint AABBs."""
+        flags = (SKIN_MATRICES if matrices else 0) | (SKIN_BOUNDS if bounds else 0) | (SKIN_KEEP_PREVIOUS if keep_previous else 0)
+        self._ck(self._lib.mi_skin_frame(self._h, C.c_uint32(flags)))
+
+    def download_joint_matrices(self, which=0, first_slot=0, n=None):
+        """-> f32[n, 16]: column-major Mat4 per slot of the current (which=0) or previous (1) buffer."""
+        n = self._n_slots - first_slot if n is None else n
+        out = np.zeros((max(n, 1), 16), np.float32)
+        self._ck(self._lib.mi_skin_download_matrices(self._h, int(which), int(first_slot), int(n), _ptr(out, C.c_float)))
+        return out[:n]
+
+    def download_skin_bounds(self, first_skin=0, n=None):
+        """-> (center f32[n, 3], half_extents f32[n, 3]) per skin; a skin without joint AABBs reports its row's Aabb as it stands."""
+        n = self._n_skins - first_skin if n is None else n
+        c, h = np.zeros((max(n, 1), 3), np.float32), np.zeros((max(n, 1), 3), np.float32)
+        self._ck(self._lib.mi_skin_download_bounds(self._h, int(first_skin), int(n), _ptr(c, C.c_float), _ptr(h, C.c_float)))
+        return c[:n], h[:n]
 
     def batch_download(self):
         """-> dict: work_items / metadata / batch_sets (lists indexed by mesh class, u32 arrays), records u32[k, 8], unbatchable

@@ -1028,7 +1028,8 @@ int32_t mi_ctx_destroy(mi_ctx* ctx) {
                       &ctx->bt_inst[0], &ctx->bt_inst[1], &ctx->bt_plan, &ctx->bt_unb, &ctx->bt_items, &ctx->bt_batches, &ctx->bt_sorted_partials,
                       &ctx->cl_row_list, &ctx->cl_remap, &ctx->cl_bind_oc, &ctx->cl_bind_idx, &ctx->cl_block_counts, &ctx->cl_pair_cb, &ctx->cl_pair_mask, &ctx->cl_acc,
                       &ctx->cl_offsets, &ctx->cl_indices, &ctx->cl_scalars, &ctx->ps_pairs[0], &ctx->ps_pairs[1], &ctx->ps_table, &ctx->ps_rows,
-                      &ctx->ps_keys, &ctx->ps_dist, &ctx->ps_count};
+                      &ctx->ps_keys, &ctx->ps_dist, &ctx->ps_count, &ctx->sk_pool, &ctx->sk_joint_rows, &ctx->sk_slot_bind, &ctx->sk_bounded, &ctx->sk_aabbs,
+                      &ctx->sk_bounds, &ctx->sk_mats[0], &ctx->sk_mats[1]};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& sl : ctx->cl_parked)  // (the parked cluster views' buffers; the selected one's are in the list above)
@@ -2589,6 +2590,8 @@ int32_t mi_device_buffer(mi_ctx* ctx, uint32_t which, void** out_ptr, uint64_t* 
     case MI_BUF_BATCH_METADATA_INDEXED: p = ctx->bt_md[1].p; bytes = ctx->bt_md[1].bytes; break;
     case MI_BUF_BATCH_SETS_NON_INDEXED: p = ctx->bt_bs[0].p; bytes = ctx->bt_bs[0].bytes; break;
     case MI_BUF_BATCH_SETS_INDEXED: p = ctx->bt_bs[1].p; bytes = ctx->bt_bs[1].bytes; break;
+    case MI_BUF_JOINT_MATRICES: p = ctx->sk_mats[ctx->sk_cur].p; bytes = (uint64_t)ctx->sk_n_slots * 64; break;
+    case MI_BUF_JOINT_MATRICES_PREVIOUS: p = ctx->sk_mats[ctx->sk_cur ^ 1u].p; bytes = (uint64_t)ctx->sk_n_slots * 64; break;
     default: return fail(ctx, MI_ERR_INVALID_ARG, "mi_device_buffer: unknown buffer %u", which);
     }
     *out_ptr = p;

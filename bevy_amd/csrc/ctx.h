@@ -1,5 +1,5 @@
 // ctx.h -- internal to the library: the context object behind the opaque mi_ctx handle and the helpers the
-// entry-point files (context.cpp, ctx_hierarchy.cpp, ctx_exchange.cpp, ctx_batch.cpp, ctx_phase_sort.cpp, ctx_cluster.cpp) share.
+// entry-point files (context.cpp, ctx_hierarchy.cpp, ctx_exchange.cpp, ctx_batch.cpp, ctx_phase_sort.cpp, ctx_skin.cpp, ctx_cluster.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -356,6 +356,15 @@ struct mi_ctx {
     enum PsState : uint32_t { PS_NONE = 0, PS_SORTED = 1, PS_EMPTY = 2 };  // what mi_phase_sort_download hands out
     uint32_t ps_state = PS_NONE;
     bool ps_lds_set = false;      // the kernels' dynamic LDS limit has been raised
+    // skinned meshes (ctx_skin.cpp, kernels_skin.hip)
+    DevBuf sk_pool;               // the inverse bindposes, 64 bytes each; sk_pool_n of them uploaded (the buffer grows with its contents)
+    DevBuf sk_joint_rows, sk_slot_bind, sk_bounded, sk_aabbs, sk_bounds, sk_mats[2];
+    std::vector<mi_skin> sk_skins;  // the last mi_skin_upload's skins (mi_skin_download_bounds: which of them have joint AABBs)
+    uint32_t sk_pool_n = 0, sk_n_slots = 0, sk_n_bounded = 0, sk_n_aabbs = 0;
+    uint32_t sk_row_end = 0;      // highest row any skin references, + 1: a mi_columns_resize below it makes mi_skin_frame MI_ERR_NOT_READY
+    uint32_t sk_mesh_lo = 0, sk_mesh_hi = 0;  // the mesh rows of the skins with joint AABBs lie in [lo, hi)
+    uint32_t sk_cur = 0;          // sk_mats[sk_cur] = the matrices of the last MI_SKIN_MATRICES frame, the other one the frame's before under MI_SKIN_KEEP_PREVIOUS
+    bool sk_uploaded = false, sk_have_cur = false, sk_have_prev = false, sk_have_bounds = false;
     DevBuf cl_remap, cl_bind_oc, cl_bind_idx, cl_block_counts, cl_pair_cb, cl_pair_mask, cl_acc, cl_offsets, cl_indices, cl_scalars;
     // derive mode of an assignment that runs in or next to the frame kernel: which rows that frame's propagate writes (cull_frame sets them)
     const uint8_t* cl_derive_changed = nullptr;

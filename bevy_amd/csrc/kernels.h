@@ -822,4 +822,29 @@ struct PhaseSortArgs {
 hipError_t set_phase_sort_lds_limit();  // once per process and device, before the first launch_phase_sort
 hipError_t launch_phase_sort(const PhaseSortArgs& a, hipStream_t stream);
 
+// ---- skinned meshes (kernels_skin.hip) ----------------------------------------------------------
+// One launch per mi_skin_frame: workgroups [0, n_mat_wgs) write joint matrices (a quad of lanes per slot, 64 slots per workgroup),
+// the ones behind them refit Aabbs (a wave per skin with joint AABBs, 4 per workgroup).  Every index below was checked on the host
+// by mi_skin_upload (ranges, rows < n, no MI_SKIN_NO_JOINT under a joint AABB): the kernel tests none of them again.
+constexpr uint32_t SKIN_NO_JOINT = 0xFFFFFFFFu;  // MI_SKIN_NO_JOINT (public header)
+constexpr uint32_t SKIN_GAP_SLOT = 0xFFFFFFFFu;  // slot_bindpose of a slot no skin owns: never written
+struct SkinBounded {  // a skin with n_aabbs > 0 (32 bytes: two scalar loads)
+    uint32_t mesh_row, first_joint, first_aabb, n_aabbs, skin, pad[3];
+};
+struct SkinArgs {
+    uint32_t n_slots, n_mat_wgs, n_bounded, n_aabbs;
+    const uint32_t* joint_rows;     // [n_slots] row of the slot's joint, or SKIN_NO_JOINT
+    const uint32_t* slot_bindpose;  // [n_slots] index into bindposes, or SKIN_GAP_SLOT
+    const float* bindposes;         // 16 floats per pool matrix, column-major
+    const float* global;            // 12 floats per row
+    float* matrices;                // [n_slots] x 16 floats, column-major
+    const SkinBounded* bounded;     // [n_bounded]
+    const uint32_t* aabbs;          // seven columns of n_aabbs words: joint (index within the skin), centre x y z, half extents x y z
+    float* aabb_center;             // the context's Aabb columns, 3 floats per row
+    float* aabb_half;
+    float* skin_bounds;             // [n_skins] x 6 floats: centre, half extents
+};
+void skin_grid(uint32_t n_slots, uint32_t n_bounded, bool matrices, bool bounds, uint32_t* n_mat_wgs, uint32_t* n_bounds_wgs);
+hipError_t launch_skin_frame(const SkinArgs& a, uint32_t n_bounds_wgs, hipStream_t stream);
+
 }  // namespace mi

@@ -803,6 +803,75 @@ int32_t mi_phase_sort_download(mi_ctx* ctx, uint32_t* out_rows, uint64_t* out_en
                                uint32_t* out_count);
 
 /* ======================================================================================= */
+/* skinned meshes: joint matrices and dynamic bounds                                       */
+/* ======================================================================================= */
+/* The two consumers of a joint's GlobalTransform, on the device, between mi_propagate and mi_cull:
+ *   joint matrices   extract_skins (bevy_pbr render/skin.rs): world_from_joint.affine() * inverse_bindpose per joint, into a
+ *                    buffer of one Mat4 per SLOT; prepare_skins' "previous frame" copy is the second buffer.
+ *   dynamic bounds   update_skinned_mesh_bounds (bevy_camera visibility): the Aabb of a mesh with DynamicSkinnedMeshBounds refitted
+ *                    from its joints' boxes, written into the Aabb column of the mesh's row -- the following cull tests the
+ *                    refitted box, and nothing is downloaded, refitted on a core and uploaded again in the middle of the frame.
+ * The reference sources were not at hand when this was written: the arithmetic stated here is the library's definition, in glam's
+ * operation order as everywhere else, and has NOT been pinned against a run of the reference.
+ *
+ *   mi_skin_upload_inverse_bindposes  matrices [first, first + n) of the pool of inverse bindposes (Mat4, column-major, 16 floats);
+ *                    the pool grows as needed, matrices never uploaded are zero.  Skins of one asset share a range.
+ *   mi_skin_upload   replaces all skins.  joint_rows[n_slots]: the row of each slot's joint, or MI_SKIN_NO_JOINT; a skin owns the
+ *                    slots [first_joint, first_joint + n_joints) of it and of the matrix buffers.  Slots no skin owns (gaps) are
+ *                    allowed and never written (the buffers are zeroed by this call).  Checked on the host, MI_ERR_INVALID_ARG with
+ *                    a message: every range lies inside its array (the bindposes inside the matrices uploaded so far); slot ranges
+ *                    of different skins are disjoint; mesh_rows are distinct; aabb.joint < n_joints; every row is below the
+ *                    context's row count (or MI_SKIN_NO_JOINT, for a joint); and -- the library's choice -- a joint AABB must not
+ *                    name a MI_SKIN_NO_JOINT joint.  A failed check leaves the previous skins in place.  Ranges of joint AABBs may
+ *                    be shared between skins.
+ *   mi_skin_frame    one kernel launch, asynchronous; call it after mi_propagate and before mi_cull (it does not ride inside
+ *                    mi_propagate_and_cull*: a frame with skins makes the two calls separately).
+ *                      MI_SKIN_MATRICES       matrix of slot s, G = GlobalTransform of joint_rows[s], B = its pool matrix:
+ *                                             Mat4::from(G) * B, each column ((x_axis b.x + y_axis b.y) + z_axis b.z) + w_axis b.w
+ *                                             with the w row computed in full.  A MI_SKIN_NO_JOINT slot gets B copied bit for bit
+ *                                             (the library's choice).
+ *                      MI_SKIN_KEEP_PREVIOUS  (with MI_SKIN_MATRICES) the buffers swap first: the matrices of the last call become
+ *                                             "previous".  Without it the current buffer is overwritten in place.
+ *                      MI_SKIN_BOUNDS         for every skin with n_aabbs > 0: E = inverse(G[mesh_row]); per joint AABB k
+ *                                             A = E * G[joint], c' = A.transform_point(center), h' = |A.matrix3| * half_extents
+ *                                             (the absolute value per element), min / max of c' -+ h' over k with _mm_min_ps /
+ *                                             _mm_max_ps semantics, then Aabb::from_min_max: center = (max + min) * 0.5,
+ *                                             half_extents = (max - min) * 0.5.  For NaN-free input the result does not depend on
+ *                                             the order of the reduction; with a NaN it is unspecified.  Written to the Aabb
+ *                                             column of mesh_row (what mi_upload_bounds writes; flags and RenderLayers stay) and
+ *                                             to a per-skin array.  A skin with n_aabbs = 0 keeps its Aabb.
+ *                    MI_ERR_NOT_READY before any mi_skin_upload, and when a mi_columns_resize has dropped a row the skins
+ *                    reference (upload the skins again); MI_ERR_INVALID_ARG for unknown flags, neither MATRICES nor BOUNDS, or
+ *                    KEEP_PREVIOUS without MATRICES.
+ *   mi_skin_download_matrices  slots [first_slot, first_slot + n) of the current (0) or previous (1) buffer; MI_ERR_NOT_READY until
+ *                    a frame has written it (previous: until a MI_SKIN_KEEP_PREVIOUS frame that followed a matrices frame).
+ *   mi_skin_download_bounds    centre and half extents of skins [first_skin, first_skin + n) after a MI_SKIN_BOUNDS frame; a skin
+ *                    with n_aabbs = 0 reports the Aabb column of its row as it stands.
+ * The buffers stay on the device as MI_BUF_JOINT_MATRICES / MI_BUF_JOINT_MATRICES_PREVIOUS (mi_device_buffer).
+ * Cost (profiles/r09_skinning/ab.md): about 200 bytes of traffic per joint for the matrices, about 100 per joint AABB; a skin with
+ * joint AABBs occupies one wave, so skins with far fewer than 64 of them leave lanes idle. */
+#define MI_SKIN_NO_JOINT 0xFFFFFFFFu
+typedef struct mi_skin {
+    uint32_t mesh_row;               /* row of the entity with SkinnedMesh (and Aabb) */
+    uint32_t first_joint, n_joints;  /* slots [first_joint, +n_joints) of joint_rows and of the matrix buffers */
+    uint32_t first_bindpose;         /* joint k uses pool matrix first_bindpose + k; skins of one asset share a range */
+    uint32_t first_aabb, n_aabbs;    /* range of joint_aabbs; 0 = no DynamicSkinnedMeshBounds: Aabb left alone */
+} mi_skin;
+typedef struct mi_joint_aabb {
+    uint32_t joint;                  /* index within the skin */
+    float center[3], half_extents[3];  /* the box, in joint space */
+} mi_joint_aabb;
+int32_t mi_skin_upload_inverse_bindposes(mi_ctx* ctx, uint32_t first, uint32_t n, const float* mat4);
+int32_t mi_skin_upload(mi_ctx* ctx, uint32_t n_skins, const mi_skin* skins, uint32_t n_slots, const uint32_t* joint_rows, uint32_t n_aabbs,
+                       const mi_joint_aabb* aabbs);
+#define MI_SKIN_MATRICES 0x1u
+#define MI_SKIN_BOUNDS 0x2u
+#define MI_SKIN_KEEP_PREVIOUS 0x4u
+int32_t mi_skin_frame(mi_ctx* ctx, uint32_t flags);
+int32_t mi_skin_download_matrices(mi_ctx* ctx, uint32_t which, uint32_t first_slot, uint32_t n, float* out16);
+int32_t mi_skin_download_bounds(mi_ctx* ctx, uint32_t first_skin, uint32_t n, float* center3, float* half3);
+
+/* ======================================================================================= */
 /* camera helpers (pure host code; what update_frusta computes, visibility/mod.rs:627-636)   */
 /* ======================================================================================= */
 
@@ -912,6 +981,8 @@ int32_t mi_exchange_download(mi_ctx* ctx, void* out_host, uint64_t bytes);
 #define MI_BUF_BATCH_METADATA_INDEXED 9
 #define MI_BUF_BATCH_SETS_NON_INDEXED 10
 #define MI_BUF_BATCH_SETS_INDEXED 11
+#define MI_BUF_JOINT_MATRICES 12          /* 64 bytes per slot; these two swap under MI_SKIN_KEEP_PREVIOUS and are valid until the next mi_skin_upload */
+#define MI_BUF_JOINT_MATRICES_PREVIOUS 13
 int32_t mi_device_buffer(mi_ctx* ctx, uint32_t which, void** out_device_ptr, uint64_t* out_bytes);
 
 /* Bench / test instrumentation (HIP-event timers, the per-kernel profile, planner and trace hooks) is declared in
