@@ -6,6 +6,15 @@ bench.py use to reach the C ABI from Python (ctypes).  There is NO CPU fallback:
 point needs a gfx950 device and raises `MiError` otherwise.
 """
 from .api import (  # noqa: F401
+    ANIM_CUBIC,
+    ANIM_LINEAR,
+    ANIM_NO_TRACK,
+    ANIM_ROTATION,
+    ANIM_SCALE,
+    ANIM_STEP,
+    ANIM_TARGET_DTYPE,
+    ANIM_TRACK_DTYPE,
+    ANIM_TRANSLATION,
     ClusterView,
     Context,
     MiError,

@@ -188,6 +188,12 @@ SKIN_NO_JOINT = 0xFFFFFFFF
 SKIN_MATRICES, SKIN_BOUNDS, SKIN_KEEP_PREVIOUS = 0x1, 0x2, 0x4
 BUF_JOINT_MATRICES, BUF_JOINT_MATRICES_PREVIOUS = 12, 13  # device_buffer(which)
 JOINT_AABB_DTYPE = np.dtype([("joint", np.uint32), ("center", np.float32, 3), ("half_extents", np.float32, 3)])  # mi_joint_aabb
+BUF_TRANSLATION, BUF_ROTATION, BUF_SCALE = 14, 15, 16  # the Transform columns
+ANIM_NO_TRACK = 0xFFFFFFFF
+ANIM_STEP, ANIM_LINEAR, ANIM_CUBIC = 0x0, 0x1, 0x2
+ANIM_TRANSLATION, ANIM_ROTATION, ANIM_SCALE = 0x00, 0x10, 0x20
+ANIM_TRACK_DTYPE = np.dtype([("first_time", np.uint32), ("n_keys", np.uint32), ("first_value", np.uint32), ("kind_interp", np.uint32)])  # mi_anim_track
+ANIM_TARGET_DTYPE = np.dtype([("row", np.uint32), ("player", np.uint32), ("track_t", np.uint32), ("track_r", np.uint32), ("track_s", np.uint32)])  # mi_anim_target
 
 ABI_SYMBOLS = [
     "mi_abi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_last_error_string", "mi_synchronize",
@@ -205,6 +211,7 @@ ABI_SYMBOLS = [
     "mi_cluster_assign_frame",
     "mi_batch_upload_rows", "mi_batch_upload_sets", "mi_batch_upload_row_bins", "mi_batch_upload_bins", "mi_batch_build", "mi_batch_build_phase",
     "mi_batch_sorted_build", "mi_upload_depth_bias", "mi_phase_sort", "mi_phase_sort_download", "mi_skin_upload_inverse_bindposes", "mi_skin_upload", "mi_skin_frame", "mi_skin_download_matrices", "mi_skin_download_bounds",
+    "mi_anim_upload_tracks", "mi_anim_upload_targets", "mi_anim_frame",
     "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
     "mi_bind_visibility_output", "mi_exchange_set_mode", "mi_exchange_configure", "mi_exchange_configure_multi", "mi_exchange_configure_owned", "mi_exchange_group_flush", "mi_exchange_last", "mi_exchange_download", "mi_device_buffer",
 ]
@@ -861,6 +868,25 @@ class Context:
         c, h = np.zeros((max(n, 1), 3), np.float32), np.zeros((max(n, 1), 3), np.float32)
         self._ck(self._lib.mi_skin_download_bounds(self._h, int(first_skin), int(n), _ptr(c, C.c_float), _ptr(h, C.c_float)))
         return c[:n], h[:n]
+
+    # animation clips
+    def anim_upload_tracks(self, tracks, times, values):
+        """Replaces the track pool (and drops the targets).  tracks: ANIM_TRACK_DTYPE[n] (kind_interp = ANIM_TRANSLATION / _ROTATION /
+        _SCALE | ANIM_STEP / _LINEAR / _CUBIC); times f32[...], values f32[...]: the pools the tracks' ranges index."""
+        tr = np.ascontiguousarray(tracks, ANIM_TRACK_DTYPE).reshape(-1)
+        tm, va = _f32(times).reshape(-1), _f32(values).reshape(-1)
+        self._ck(self._lib.mi_anim_upload_tracks(self._h, len(tr), tr.ctypes.data_as(C.c_void_p) if len(tr) else None, len(tm),
+                                                 _ptr(tm, C.c_float) if len(tm) else None, len(va), _ptr(va, C.c_float) if len(va) else None))
+
+    def anim_upload_targets(self, targets):
+        """targets: ANIM_TARGET_DTYPE[n]: the row each one writes, its player, and a track (or ANIM_NO_TRACK) per component."""
+        tg = np.ascontiguousarray(targets, ANIM_TARGET_DTYPE).reshape(-1)
+        self._ck(self._lib.mi_anim_upload_targets(self._h, len(tg), tg.ctypes.data_as(C.c_void_p) if len(tg) else None))
+
+    def anim_frame(self, seek_times):
+        """Before propagate: every target's Transform from its tracks at seek_times[player] (f32, one per player)."""
+        st = _f32(seek_times).reshape(-1)
+        self._ck(self._lib.mi_anim_frame(self._h, len(st), _ptr(st, C.c_float) if len(st) else None, C.c_uint32(0)))
 
     def batch_download(self):
         """-> dict: work_items / metadata / batch_sets (lists indexed by mesh class, u32 arrays), records u32[k, 8], unbatchable

@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbevy_mi355x.so")
-SOURCES = ["kernels_flat.hip", "kernels_tree.hip", "kernels_cluster.hip", "kernels_batch.hip", "kernels_sorted.hip", "kernels_cells.hip", "kernels_phase_sort.hip", "kernels_skin.hip", "context.cpp", "ctx_hierarchy.cpp", "ctx_exchange.cpp",
-           "ctx_batch.cpp", "ctx_phase_sort.cpp", "ctx_skin.cpp", "ctx_cluster.cpp", "host_helpers.cpp"]
+SOURCES = ["kernels_flat.hip", "kernels_tree.hip", "kernels_cluster.hip", "kernels_batch.hip", "kernels_sorted.hip", "kernels_cells.hip", "kernels_phase_sort.hip", "kernels_skin.hip", "kernels_anim.hip", "context.cpp", "ctx_hierarchy.cpp", "ctx_exchange.cpp",
+           "ctx_batch.cpp", "ctx_phase_sort.cpp", "ctx_skin.cpp", "ctx_anim.cpp", "ctx_cluster.cpp", "host_helpers.cpp"]
 HEADERS = ["kernels.h", "ctx.h", "glam_math.h", "visibility_rule.h", "cluster_walk.h", "cluster_fill.h", "compact_fast.h", "strip_plan.h", os.path.join("..", "..", "include", "bevy_mi355x.h"), os.path.join("..", "..", "include", "bevy_mi355x_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value"]
@@ -26,9 +26,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
 FILE_FLAGS = {"kernels_flat.hip": ["-fno-slp-vectorize"], "kernels_tree.hip": ["-fno-slp-vectorize"],
               "kernels_cluster.hip": ["-fno-slp-vectorize"],
               "kernels_phase_sort.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-              "kernels_skin.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "kernels_skin.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "kernels_anim.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # (kernels_phase_sort.hip: its four f32 multiplies and adds per item stay scalar instructions -- no v_pk_* forms)
 # (kernels_skin.hip: a float kernel like the first three, and no v_pk_* forms either)
+# (kernels_anim.hip: the same float flags as kernels_skin.hip)
 # (kernels_cells.hip: the build of the static cull order -- a radix sort from rocPRIM's headers and three small kernels; default flags)
 
 

@@ -1029,7 +1029,7 @@ int32_t mi_ctx_destroy(mi_ctx* ctx) {
                       &ctx->cl_row_list, &ctx->cl_remap, &ctx->cl_bind_oc, &ctx->cl_bind_idx, &ctx->cl_block_counts, &ctx->cl_pair_cb, &ctx->cl_pair_mask, &ctx->cl_acc,
                       &ctx->cl_offsets, &ctx->cl_indices, &ctx->cl_scalars, &ctx->ps_pairs[0], &ctx->ps_pairs[1], &ctx->ps_table, &ctx->ps_rows,
                       &ctx->ps_keys, &ctx->ps_dist, &ctx->ps_count, &ctx->sk_pool, &ctx->sk_joint_rows, &ctx->sk_slot_bind, &ctx->sk_bounded, &ctx->sk_aabbs,
-                      &ctx->sk_bounds, &ctx->sk_mats[0], &ctx->sk_mats[1]};
+                      &ctx->sk_bounds, &ctx->sk_mats[0], &ctx->sk_mats[1], &ctx->an_tracks, &ctx->an_times, &ctx->an_values, &ctx->an_targets, &ctx->an_wg_times};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& sl : ctx->cl_parked)  // (the parked cluster views' buffers; the selected one's are in the list above)
@@ -1261,17 +1261,69 @@ int32_t mi_upload_transforms(mi_ctx* ctx, uint32_t first_row, uint32_t n, const 
     return MI_OK;
 }
 
-// rows / t / r / s lie in the pinned arena: one scatter kernel reads them over PCIe and raises the rows' change bytes
-// window_order: +1 / -1 = the rows lie in an upload window (they stay put until the windows are recycled) and strictly ascend / descend
-static int32_t scatter_indexed(mi_ctx* ctx, const uint32_t* rows, const float* t, const float* r, const float* s, uint32_t n,
-                               int window_order = 0) {
+}  // extern "C"
+namespace mi_detail {
+// What an indexed write of Transforms does to the context's state, around its one launch -- shared by the scatter of an indexed
+// upload below and by mi_anim_frame (ctx_anim.cpp), which computes the same rows' Transforms on the device.
+// begin: nothing fetched or written ahead applies any more; first use of the change column; a cluster assignment still reading
+// the columns is joined; and the launch is told whether it is also the frame's mark_dirty_trees for its rows (w).  The caller
+// touches the scale part of the row summary itself: it knows which rows carry a scale.
+int32_t indexed_write_begin(mi_ctx* ctx, IndexedWrite* w) {
     trs_written(ctx);
-    // ---- GlobalTransforms ahead of the changed-rows frame (ctx.h): only when this upload's rows will be exactly the frame's ----
-    const bool column_clean = !ctx->changed_maybe && (ctx->have_changed || ctx->propagated_rows >= ctx->n);
     if (ctx->gs_k && !ctx->gs_used && ctx->chunk_mode != 2) ctx->sparse_ahead_wanted = false;  // (the last one was written for nothing)
     ctx->gs_k = 0;
     ctx->gs_frame_ok = false;
     ctx->gs_used = false;
+    if (!ctx->have_changed) {
+        // First use of the change column: rows a propagate has already consumed count as unchanged from here on.  Rows
+        // that have not been through one yet are still Added<GlobalTransform> (systems.rs:45-50) and keep their mark.
+        if (ctx->propagated_rows)
+            HIP_TRY(ctx, hipMemsetAsync(ctx->changed, 0, std::min(ctx->propagated_rows, ctx->n), ctx->stream));
+        ctx->have_changed = true;
+    }
+    int32_t rc = cluster_join(ctx);
+    if (rc) return rc;
+    ctx->cl_inputs_dirty = true;
+    // mark_dirty_trees for these rows in the same launch, when the frames run under the static-scene rule and the half the next
+    // propagate will read holds nothing but such marks
+    w->mark_here = ctx->have_hierarchy && ctx->marks_live && ctx->tree_bytes && ctx->parent_idx.p &&
+                   (ctx->marks_in_cur || ctx->tree_clean[ctx->tree_parity]);
+    w->parent_idx = w->mark_here ? (const uint32_t*)ctx->parent_idx.p : nullptr;
+    w->mark_cur = w->mark_here ? ctx->tree_bytes + (size_t)ctx->tree_parity * ctx->tree_half_words * 4 : nullptr;
+    w->clear_other = nullptr;
+    if (w->mark_here && !ctx->marks_other_cleared && !ctx->tree_clean[ctx->tree_parity ^ 1u])
+        w->clear_other = (uint32_t*)(ctx->tree_bytes + (size_t)(ctx->tree_parity ^ 1u) * ctx->tree_half_words * 4);
+    w->n_clear_words = ctx->tree_half_words;
+    w->anc = ctx->anc_valid ? (const uint32_t*)ctx->anc.p : nullptr;
+    return MI_OK;
+}
+// end: the launch is enqueued -- n rows carry this generation's stamp, and the marks are where w said
+void indexed_write_end(mi_ctx* ctx, const IndexedWrite& w, uint32_t n) {
+    if (w.mark_here) {
+        if (!ctx->marks_in_cur) ctx->marks_complete = !ctx->changed_maybe;  // complete so far iff nothing was marked changed before this upload
+        ctx->marks_in_cur = true;
+        if (w.clear_other) {
+            ctx->marks_other_cleared = true;
+            ctx->tree_clean[ctx->tree_parity ^ 1u] = true;
+        }
+    } else {
+        ctx->marks_complete = false;
+    }
+    ctx->changed_maybe = true, ++ctx->marks_serial;
+    if (ctx->changed_rows_hint != UINT64_MAX) ctx->changed_rows_hint += n;
+}
+}  // namespace mi_detail
+extern "C" {
+
+// rows / t / r / s lie in the pinned arena: one scatter kernel reads them over PCIe and raises the rows' change bytes
+// window_order: +1 / -1 = the rows lie in an upload window (they stay put until the windows are recycled) and strictly ascend / descend
+static int32_t scatter_indexed(mi_ctx* ctx, const uint32_t* rows, const float* t, const float* r, const float* s, uint32_t n,
+                               int window_order = 0) {
+    // ---- GlobalTransforms ahead of the changed-rows frame (ctx.h): only when this upload's rows will be exactly the frame's ----
+    const bool column_clean = !ctx->changed_maybe && (ctx->have_changed || ctx->propagated_rows >= ctx->n);
+    IndexedWrite w{};
+    int32_t rc = indexed_write_begin(ctx, &w);
+    if (rc) return rc;
     float* g_ahead = nullptr;
     if (window_order != 0 && column_clean && ctx->chunk_mode != 1 && (ctx->sparse_ahead_wanted || ctx->chunk_mode == 2) && !ctx->have_hierarchy &&
         !ctx->xch.on) {
@@ -1293,16 +1345,6 @@ static int32_t scatter_indexed(mi_ctx* ctx, const uint32_t* rows, const float* t
     if (t) HIP_TRY(ctx, hipHostGetDevicePointer(&d_t, (void*)t, 0));
     if (r) HIP_TRY(ctx, hipHostGetDevicePointer(&d_r, (void*)r, 0));
     if (s) HIP_TRY(ctx, hipHostGetDevicePointer(&d_s, (void*)s, 0));
-    if (!ctx->have_changed) {
-        // First use of the change column: rows a propagate has already consumed count as unchanged from here on.  Rows
-        // that have not been through one yet are still Added<GlobalTransform> (systems.rs:45-50) and keep their mark.
-        if (ctx->propagated_rows)
-            HIP_TRY(ctx, hipMemsetAsync(ctx->changed, 0, std::min(ctx->propagated_rows, ctx->n), ctx->stream));
-        ctx->have_changed = true;
-    }
-    int32_t rc = cluster_join(ctx);
-    if (rc) return rc;
-    ctx->cl_inputs_dirty = true;
     if (s) {  // the scale part of the row summary: a range that certainly covers the rows (a window without scale leaves it alone)
         if (window_order != 0) {  // (strictly monotonic: the first and the last entry are the ends)
             const uint32_t a = std::min(rows[0], rows[n - 1u]), b = std::max(rows[0], rows[n - 1u]);
@@ -1311,29 +1353,10 @@ static int32_t scatter_indexed(mi_ctx* ctx, const uint32_t* rows, const float* t
             row_summary_touch(ctx, ROWSUM_PART_SCALE, 0, ctx->n);
         }
     }
-    // mark_dirty_trees for these rows in the same launch, when the frames run under the static-scene rule and the half the next
-    // propagate will read holds nothing but such marks
-    const bool mark_here = ctx->have_hierarchy && ctx->marks_live && ctx->tree_bytes && ctx->parent_idx.p &&
-                           (ctx->marks_in_cur || ctx->tree_clean[ctx->tree_parity]);
-    uint8_t* const cur = mark_here ? ctx->tree_bytes + (size_t)ctx->tree_parity * ctx->tree_half_words * 4 : nullptr;
-    uint32_t* other = nullptr;
-    if (mark_here && !ctx->marks_other_cleared && !ctx->tree_clean[ctx->tree_parity ^ 1u])
-        other = (uint32_t*)(ctx->tree_bytes + (size_t)(ctx->tree_parity ^ 1u) * ctx->tree_half_words * 4);
     HIP_TRY(ctx, launch_upload_trs_indexed((const uint32_t*)d_rows, (const float*)d_t, (const float*)d_r, (const float*)d_s, n, ctx->t, ctx->r,
-                                           ctx->s, ctx->changed, ctx->changed_gen, ctx->stream, mark_here ? (const uint32_t*)ctx->parent_idx.p : nullptr,
-                                           cur, other, ctx->tree_half_words, ctx->anc_valid ? (const uint32_t*)ctx->anc.p : nullptr, g_ahead, window_order < 0));
-    if (mark_here) {
-        if (!ctx->marks_in_cur) ctx->marks_complete = !ctx->changed_maybe;  // complete so far iff nothing was marked changed before this upload
-        ctx->marks_in_cur = true;
-        if (other) {
-            ctx->marks_other_cleared = true;
-            ctx->tree_clean[ctx->tree_parity ^ 1u] = true;
-        }
-    } else {
-        ctx->marks_complete = false;
-    }
-    ctx->changed_maybe = true, ++ctx->marks_serial;
-    if (ctx->changed_rows_hint != UINT64_MAX) ctx->changed_rows_hint += n;
+                                           ctx->s, ctx->changed, ctx->changed_gen, ctx->stream, w.parent_idx, w.mark_cur, w.clear_other,
+                                           w.n_clear_words, w.anc, g_ahead, window_order < 0));
+    indexed_write_end(ctx, w, n);
     if (g_ahead) {
         ctx->gs_k = n;
         ctx->gs_rows = rows;
@@ -2592,6 +2615,9 @@ int32_t mi_device_buffer(mi_ctx* ctx, uint32_t which, void** out_ptr, uint64_t* 
     case MI_BUF_BATCH_SETS_INDEXED: p = ctx->bt_bs[1].p; bytes = ctx->bt_bs[1].bytes; break;
     case MI_BUF_JOINT_MATRICES: p = ctx->sk_mats[ctx->sk_cur].p; bytes = (uint64_t)ctx->sk_n_slots * 64; break;
     case MI_BUF_JOINT_MATRICES_PREVIOUS: p = ctx->sk_mats[ctx->sk_cur ^ 1u].p; bytes = (uint64_t)ctx->sk_n_slots * 64; break;
+    case MI_BUF_TRANSLATION: p = ctx->t; bytes = (uint64_t)ctx->n * 12; break;
+    case MI_BUF_ROTATION: p = ctx->r; bytes = (uint64_t)ctx->n * 16; break;
+    case MI_BUF_SCALE: p = ctx->s; bytes = (uint64_t)ctx->n * 12; break;
     default: return fail(ctx, MI_ERR_INVALID_ARG, "mi_device_buffer: unknown buffer %u", which);
     }
     *out_ptr = p;

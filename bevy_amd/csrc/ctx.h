@@ -1,5 +1,5 @@
 // ctx.h -- internal to the library: the context object behind the opaque mi_ctx handle and the helpers the
-// entry-point files (context.cpp, ctx_hierarchy.cpp, ctx_exchange.cpp, ctx_batch.cpp, ctx_phase_sort.cpp, ctx_skin.cpp, ctx_cluster.cpp) share.
+// entry-point files (context.cpp, ctx_hierarchy.cpp, ctx_exchange.cpp, ctx_batch.cpp, ctx_phase_sort.cpp, ctx_skin.cpp, ctx_anim.cpp, ctx_cluster.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -365,6 +365,15 @@ struct mi_ctx {
     uint32_t sk_mesh_lo = 0, sk_mesh_hi = 0;  // the mesh rows of the skins with joint AABBs lie in [lo, hi)
     uint32_t sk_cur = 0;          // sk_mats[sk_cur] = the matrices of the last MI_SKIN_MATRICES frame, the other one the frame's before under MI_SKIN_KEEP_PREVIOUS
     bool sk_uploaded = false, sk_have_cur = false, sk_have_prev = false, sk_have_bounds = false;
+    // animation clips (ctx_anim.cpp, kernels_anim.hip)
+    DevBuf an_tracks, an_times, an_values;  // the track pool: 16-byte descriptors, key times, key values
+    DevBuf an_targets, an_wg_times;         // five columns of an_n_targets words in launch order (by player, by row); the times a workgroup stages
+    std::vector<mi_anim_track> an_tracks_host;  // the pool's descriptors (mi_anim_upload_targets checks against them)
+    uint32_t an_n_targets = 0;
+    uint32_t an_row_end = 0;      // highest row any target writes, + 1: a mi_columns_resize below it makes mi_anim_frame MI_ERR_NOT_READY
+    uint32_t an_player_end = 0;   // highest player any target names, + 1
+    uint32_t an_scale_lo = 0, an_scale_hi = 0;  // the rows of the targets with a scale track lie in [lo, hi] (an_any_scale)
+    bool an_have_tracks = false, an_have_targets = false, an_any_scale = false;
     DevBuf cl_remap, cl_bind_oc, cl_bind_idx, cl_block_counts, cl_pair_cb, cl_pair_mask, cl_acc, cl_offsets, cl_indices, cl_scalars;
     // derive mode of an assignment that runs in or next to the frame kernel: which rows that frame's propagate writes (cull_frame sets them)
     const uint8_t* cl_derive_changed = nullptr;
@@ -518,6 +527,19 @@ int32_t download(mi_ctx* ctx, void* dst, const void* src, size_t bytes);
 int32_t check_rows(mi_ctx* ctx, uint32_t first, uint32_t n, const char* what);
 void row_summary_touch(mi_ctx* ctx, uint32_t parts, uint32_t first_row, uint32_t n_rows);  // the columns of these rows were written
 int32_t row_summary_ensure(mi_ctx* ctx);
+// The state around a launch that writes the Transforms of listed rows and stamps their change bytes (context.cpp: the scatter of
+// an indexed upload; ctx_anim.cpp: mi_anim_frame).  What begin fills in is what the launch needs to be the frame's mark_dirty_trees
+// for its rows as well (all nullptr: it is not).
+struct IndexedWrite {
+    bool mark_here;
+    const uint32_t* parent_idx;
+    uint8_t* mark_cur;      // the half of the TransformTreeChanged bytes the next propagate reads
+    uint32_t* clear_other;  // the other half, when this launch is to zero it (n_clear_words words)
+    uint32_t n_clear_words;
+    const uint32_t* anc;
+};
+int32_t indexed_write_begin(mi_ctx* ctx, IndexedWrite* w);
+void indexed_write_end(mi_ctx* ctx, const IndexedWrite& w, uint32_t n);
 void trs_written(mi_ctx* ctx);  // the Transform columns (or the numbering / count of rows) changed: nothing fetched ahead applies any more
 int32_t consume_changed(mi_ctx* ctx);  // the propagate has read the change column: every row is unchanged from here on
 void prof_close(mi_ctx* ctx);

@@ -1,0 +1,153 @@
+// ctx_anim.cpp -- animation clips: the entry points in front of kernels_anim.hip.  The two uploads check every index the kernel
+// will follow (it tests none of them again) and lay the targets out for it; mi_anim_frame is one launch, and to the context's state
+// what an indexed Transform upload of the same rows is (indexed_write_begin / _end, context.cpp).
+#include "ctx.h"
+
+using namespace mi;
+using namespace mi_detail;
+
+namespace {
+uint32_t anim_width(uint32_t kind_interp) { return (kind_interp & ~ANIM_INTERP_MASK) == ANIM_ROTATION ? 4u : 3u; }
+}  // namespace
+
+extern "C" {
+
+int32_t mi_anim_upload_tracks(mi_ctx* ctx, uint32_t n_tracks, const mi_anim_track* tracks, uint32_t n_times, const float* times, uint32_t n_values,
+                              const float* values) {
+    ENTER(ctx);
+    if ((n_tracks && !tracks) || (n_times && !times) || (n_values && !values)) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_tracks: NULL array");
+    // ---- validation: nothing of the previous pool is touched before it has passed ----
+    for (uint32_t i = 0; i < n_tracks; ++i) {
+        const mi_anim_track& tr = tracks[i];
+        const uint32_t interp = tr.kind_interp & ANIM_INTERP_MASK, comp = tr.kind_interp & ~ANIM_INTERP_MASK;
+        if (interp > ANIM_CUBIC) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_tracks: track %u: unknown interpolation in kind_interp 0x%x", i, tr.kind_interp);
+        if (comp != ANIM_TRANSLATION && comp != ANIM_ROTATION && comp != ANIM_SCALE)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_tracks: track %u: unknown component in kind_interp 0x%x", i, tr.kind_interp);
+        if (tr.n_keys == 0) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_tracks: track %u has no keys", i);
+        if ((uint64_t)tr.first_time + tr.n_keys > n_times)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_tracks: track %u: times [%u,+%u) exceed %u", i, tr.first_time, tr.n_keys, n_times);
+        const uint64_t floats = (uint64_t)tr.n_keys * anim_width(tr.kind_interp) * (interp == ANIM_CUBIC ? 3u : 1u);
+        if ((uint64_t)tr.first_value + floats > n_values)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_tracks: track %u: values [%u,+%llu) exceed %u", i, tr.first_value, (unsigned long long)floats, n_values);
+        const float* t = times + tr.first_time;
+        for (uint32_t k = 1; k < tr.n_keys; ++k)
+            if (!(t[k] > t[k - 1u])) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_tracks: track %u: times not strictly ascending at key %u", i, k);
+    }
+    int32_t rc;
+    if ((rc = ensure(ctx, ctx->an_tracks, (size_t)n_tracks * sizeof(mi_anim_track)))) return rc;
+    if ((rc = ensure(ctx, ctx->an_times, (size_t)n_times * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_values, (size_t)n_values * 4))) return rc;
+    ctx->an_have_tracks = ctx->an_have_targets = false;
+    if ((rc = upload(ctx, ctx->an_tracks.p, tracks, (size_t)n_tracks * sizeof(mi_anim_track)))) return rc;
+    if ((rc = upload(ctx, ctx->an_times.p, times, (size_t)n_times * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_values.p, values, (size_t)n_values * 4))) return rc;
+    ctx->an_tracks_host.assign(tracks, tracks + n_tracks);
+    ctx->an_n_targets = 0;
+    ctx->an_have_tracks = true;
+    return MI_OK;
+}
+
+int32_t mi_anim_upload_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_target* targets) {
+    ENTER(ctx);
+    if (n_targets && !targets) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_targets: NULL");
+    if (!ctx->an_have_tracks) return fail(ctx, MI_ERR_NOT_READY, "mi_anim_upload_targets before mi_anim_upload_tracks");
+    // ---- validation: nothing of the previous targets is touched before it has passed ----
+    const std::vector<mi_anim_track>& pool = ctx->an_tracks_host;
+    static const char* const field[3] = {"track_t", "track_r", "track_s"};
+    static const uint32_t comp_of[3] = {ANIM_TRANSLATION, ANIM_ROTATION, ANIM_SCALE};
+    uint32_t row_end = 0, player_end = 0, scale_lo = 0xFFFFFFFFu, scale_hi = 0;
+    for (uint32_t i = 0; i < n_targets; ++i) {
+        const mi_anim_target& tg = targets[i];
+        if (tg.row >= ctx->n) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_targets: target %u: row %u >= %u live rows", i, tg.row, ctx->n);
+        if (tg.player == 0xFFFFFFFFu) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_targets: target %u: player 0x%x", i, tg.player);
+        const uint32_t tr[3] = {tg.track_t, tg.track_r, tg.track_s};
+        for (uint32_t c = 0; c < 3; ++c) {
+            if (tr[c] == MI_ANIM_NO_TRACK) continue;
+            if (tr[c] >= pool.size()) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_targets: target %u: %s %u >= %zu tracks", i, field[c], tr[c], pool.size());
+            if ((pool[tr[c]].kind_interp & ~ANIM_INTERP_MASK) != comp_of[c])
+                return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_targets: target %u: %s %u is a track of another component (kind_interp 0x%x)", i, field[c], tr[c],
+                            pool[tr[c]].kind_interp);
+        }
+        row_end = std::max(row_end, tg.row + 1u);
+        player_end = std::max(player_end, tg.player + 1u);
+        if (tg.track_s != MI_ANIM_NO_TRACK) scale_lo = std::min(scale_lo, tg.row), scale_hi = std::max(scale_hi, tg.row);
+    }
+    // ---- the launch order: by player, by row (rows are distinct: adjacent equals after the sort are the duplicates) ----
+    std::vector<uint32_t> order(n_targets);
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return targets[x].row < targets[y].row; });
+    for (uint32_t i = 1; i < n_targets; ++i)
+        if (targets[order[i]].row == targets[order[i - 1u]].row) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_targets: row %u belongs to two targets", targets[order[i]].row);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return targets[x].player < targets[y].player; });
+    std::vector<uint32_t> soa((size_t)5 * n_targets);
+    const uint32_t n_wgs = (n_targets + ANIM_THREADS - 1u) / ANIM_THREADS;
+    std::vector<uint32_t> wg_times((size_t)2 * n_wgs, 0u);
+    for (uint32_t w = 0; w < n_wgs; ++w) {
+        uint64_t lo = UINT64_MAX, hi = 0;  // the range of key times this workgroup's tracks use
+        for (uint32_t i = w * ANIM_THREADS; i < std::min(n_targets, (w + 1u) * ANIM_THREADS); ++i) {
+            const mi_anim_target& tg = targets[order[i]];
+            const uint32_t col[5] = {tg.row, tg.player, tg.track_t, tg.track_r, tg.track_s};
+            for (uint32_t c = 0; c < 5; ++c) soa[(size_t)c * n_targets + i] = col[c];
+            for (uint32_t c = 2; c < 5; ++c) {
+                if (col[c] == MI_ANIM_NO_TRACK) continue;
+                lo = std::min<uint64_t>(lo, pool[col[c]].first_time);
+                hi = std::max<uint64_t>(hi, (uint64_t)pool[col[c]].first_time + pool[col[c]].n_keys);
+            }
+        }
+        if (lo < hi && hi - lo <= ANIM_LDS_TIMES) wg_times[2u * w] = (uint32_t)lo, wg_times[2u * w + 1u] = (uint32_t)(hi - lo);
+    }
+    int32_t rc;
+    if ((rc = ensure(ctx, ctx->an_targets, soa.size() * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_wg_times, wg_times.size() * 4))) return rc;
+    ctx->an_have_targets = false;
+    if ((rc = upload(ctx, ctx->an_targets.p, soa.data(), soa.size() * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_wg_times.p, wg_times.data(), wg_times.size() * 4))) return rc;
+    ctx->an_n_targets = n_targets;
+    ctx->an_row_end = row_end;
+    ctx->an_player_end = player_end;
+    ctx->an_any_scale = scale_lo <= scale_hi;
+    ctx->an_scale_lo = ctx->an_any_scale ? scale_lo : 0u;
+    ctx->an_scale_hi = scale_hi;
+    ctx->an_have_targets = true;
+    return MI_OK;
+}
+
+int32_t mi_anim_frame(mi_ctx* ctx, uint32_t n_players, const float* seek_time, uint32_t flags) {
+    ENTER(ctx);
+    if (flags) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame: flags 0x%x", flags);
+    if (!ctx->an_have_tracks || !ctx->an_have_targets) return fail(ctx, MI_ERR_NOT_READY, "mi_anim_frame before mi_anim_upload_tracks and mi_anim_upload_targets");
+    if (ctx->an_row_end > ctx->n)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_frame: the targets write row %u, the context has %u rows (upload the targets again)", ctx->an_row_end - 1u, ctx->n);
+    if (ctx->an_player_end > n_players) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame: a target names player %u, n_players = %u", ctx->an_player_end - 1u, n_players);
+    if (ctx->an_n_targets == 0) return MI_OK;
+    if (!seek_time) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame: NULL");
+    void *st = nullptr, *d_seek = nullptr;
+    int32_t rc = stage_alloc(ctx, (size_t)n_players * 4, &st);
+    if (rc) return rc;
+    memcpy(st, seek_time, (size_t)n_players * 4);
+    HIP_TRY(ctx, hipHostGetDevicePointer(&d_seek, st, 0));
+    IndexedWrite w{};
+    if ((rc = indexed_write_begin(ctx, &w))) return rc;
+    if (ctx->an_any_scale) row_summary_touch(ctx, ROWSUM_PART_SCALE, ctx->an_scale_lo, ctx->an_scale_hi - ctx->an_scale_lo + 1u);
+    AnimArgs a{};
+    a.n_targets = ctx->an_n_targets;
+    a.targets = (const uint32_t*)ctx->an_targets.p;
+    a.wg_times = (const uint32_t*)ctx->an_wg_times.p;
+    a.tracks = (const uint32_t*)ctx->an_tracks.p;
+    a.times = (const float*)ctx->an_times.p;
+    a.values = (const float*)ctx->an_values.p;
+    a.seek = (const float*)d_seek;
+    a.t = ctx->t, a.r = ctx->r, a.s = ctx->s;
+    a.changed = ctx->changed;
+    a.changed_gen = ctx->changed_gen;
+    a.parent_idx = w.parent_idx;
+    a.mark_bytes = w.mark_cur;
+    a.clear_words = w.clear_other;
+    a.n_clear_words = w.n_clear_words;
+    a.anc = w.anc;
+    HIP_TRY(ctx, launch_anim_frame(a, ctx->stream));
+    indexed_write_end(ctx, w, ctx->an_n_targets);
+    return MI_OK;
+}
+
+}  // extern "C"

@@ -847,4 +847,33 @@ struct SkinArgs {
 void skin_grid(uint32_t n_slots, uint32_t n_bounded, bool matrices, bool bounds, uint32_t* n_mat_wgs, uint32_t* n_bounds_wgs);
 hipError_t launch_skin_frame(const SkinArgs& a, uint32_t n_bounds_wgs, hipStream_t stream);
 
+// ---- animation clips (kernels_anim.hip) ----------------------------------------------------------
+// One launch per mi_anim_frame: a lane per target, 256 targets per workgroup, in the order mi_anim_upload_targets laid them out (by
+// player, by row).  Every index below was checked on the host by the two uploads: the kernel tests none of them again.
+constexpr uint32_t ANIM_NO_TRACK = 0xFFFFFFFFu;  // MI_ANIM_NO_TRACK (public header)
+constexpr uint32_t ANIM_STEP = 0u, ANIM_LINEAR = 1u, ANIM_CUBIC = 2u, ANIM_INTERP_MASK = 0xFu;  // MI_ANIM_* (public header)
+constexpr uint32_t ANIM_TRANSLATION = 0x00u, ANIM_ROTATION = 0x10u, ANIM_SCALE = 0x20u;
+constexpr uint32_t ANIM_THREADS = 256u;
+constexpr uint32_t ANIM_LDS_TIMES = 2048u;  // key times a workgroup stages in LDS (8 KB); a workgroup whose tracks span more searches global memory
+struct AnimArgs {
+    uint32_t n_targets;
+    uint32_t n_target_wgs;       // workgroups [0, n_target_wgs) own targets; the ones behind them only help zeroing clear_words
+    const uint32_t* targets;     // five columns of n_targets words: row, player, track_t, track_r, track_s
+    const uint32_t* wg_times;    // two words per target workgroup: first and count of the range of `times` it stages (count 0: none)
+    const uint32_t* tracks;      // four words per track: first_time, n_keys, first_value, kind_interp
+    const float* times;
+    const float* values;
+    const float* seek;           // [n_players], pinned host memory mapped into the device
+    float *t, *r, *s;            // the Transform columns
+    uint8_t* changed;
+    uint32_t changed_gen;
+    // as k_upload_trs_indexed: mark_bytes != nullptr = this launch is mark_dirty_trees for its rows; clear_words: zeroed by it
+    const uint32_t* parent_idx;
+    uint8_t* mark_bytes;
+    uint32_t* clear_words;
+    uint32_t n_clear_words;
+    const uint32_t* anc;
+};
+hipError_t launch_anim_frame(AnimArgs a, hipStream_t stream);
+
 }  // namespace mi

@@ -872,6 +872,77 @@ int32_t mi_skin_download_matrices(mi_ctx* ctx, uint32_t which, uint32_t first_sl
 int32_t mi_skin_download_bounds(mi_ctx* ctx, uint32_t first_skin, uint32_t n, float* center3, float* half3);
 
 /* ======================================================================================= */
+/* animation clips: keyframe tracks sampled into Transforms                                */
+/* ======================================================================================= */
+/* The stage in front of mi_propagate for animated rigs: what animate_targets (bevy_animation) writes into the Transform of every
+ * animation target of a player that plays ONE clip at weight 1, computed on the device from a resident pool of keyframe tracks and
+ * one float per player -- its seek time -- instead of being sampled on a core and uploaded, 40 bytes per joint and frame.
+ * Out of scope: blend graphs, transitions between clips, morph weights, and advancing the players' clocks.  The host advances
+ * seek_time per player and keeps the stock system for blended players.
+ * The reference sources were not at hand when this was written: the arithmetic stated here is the library's definition, in glam's
+ * operation order as everywhere else, and has NOT been pinned against a run of the reference.
+ *
+ *   mi_anim_upload_tracks   replaces the track pool -- and drops the targets, which name tracks by index: upload them afterwards.
+ *                    A track is n_keys key times times[first_time ..] and their values from values[first_value ..]: 3 floats per
+ *                    key for translation and scale, 4 for rotation (x, y, z, w); a MI_ANIM_CUBIC track holds three such values
+ *                    per key, in glTF order: in-tangent, value, out-tangent.  kind_interp = component | interpolation.  Tracks
+ *                    may share a range of times (glTF samplers that share an input accessor do), and waves whose tracks do find
+ *                    the key interval once.  Checked on the host, MI_ERR_INVALID_ARG with a message: every range lies inside its
+ *                    pool; n_keys >= 1; times strictly ascending within a track (which refuses a NaN); component and interpolation
+ *                    codes are known.  A failed check leaves the previous pool (and targets) in place.
+ *   mi_anim_upload_targets  replaces the targets.  A target writes row `row` from the tracks it names, sampled at the seek time of
+ *                    player `player`; MI_ANIM_NO_TRACK = that component of the row is left alone.  Checked: rows are below the
+ *                    row count and distinct; track indices are in range, and each track is of the matching component.  The
+ *                    library reorders the targets (by player, by row); the caller's order carries no meaning.
+ *   mi_anim_frame    one kernel launch, asynchronous; call it before mi_propagate.  For every target: the t / r / s columns of its
+ *                    row from its tracks at seek_time[player], and the row's change byte -- the device-computed twin of
+ *                    mi_upload_transforms_indexed for those rows, with everything that call does to the context's state.
+ *                    flags: none defined, pass 0.  MI_ERR_NOT_READY before both uploads, and when a mi_columns_resize has
+ *                    dropped a row the targets write (upload the targets again); MI_ERR_INVALID_ARG when a target's player is
+ *                    >= n_players.  The seek times travel in the pinned staging block: no copy is launched in front.
+ * Sampling a track with times T[0..k) at seek time x, every operation rounded on its own (no fused multiply-add):
+ *     k == 1, x <= T[0], or x is NaN (the library's choice)   the first key's value, bit for bit
+ *     x >= T[k-1]                                             the last key's value, bit for bit
+ *     otherwise  i = the largest index with T[i] <= x;  x == T[i] -> key i's value, bit for bit (the library's choice: no
+ *                interpolation at u = 0);  else d = T[i+1] - T[i], u = (x - T[i]) / d, a = value i, b = value i + 1 and
+ *       MI_ANIM_STEP     a, bit for bit
+ *       MI_ANIM_LINEAR   translation, scale: a + (b - a) * u per component
+ *                        rotation: Quat::slerp -- dot = (x x' + z z') + (y y' + w w'); dot < 0: b = -b, dot = -dot;
+ *                        dot > 0.9995: normalize(a + (b - a) * u); else th = acos(dot),
+ *                        (a * sin(th * (1 - u)) + b * sin(th * u)) * (1 / sin(th))
+ *       MI_ANIM_CUBIC    u2 = u u, u3 = u2 u;  ((h00 a + h10 out_i) + h01 b) + h11 in_{i+1}  per component, with
+ *                        h00 = (2 u3 - 3 u2) + 1, h10 = d ((u3 - 2 u2) + u), h01 = 3 u2 - 2 u3, h11 = d (u3 - u2)
+ *                        (Hermite with glTF's tangent scaling); a rotation is normalized afterwards
+ *     normalize(q) = q / sqrt((x x + z z) + (y y + w w)) per component.  acos and sin are the device's, correctly rounded neither
+ *     here nor in the reference: rotations of LINEAR and CUBIC tracks agree with an exact evaluation to a few ulp of 1, not bit for bit.
+ * The Transform columns stay on the device as MI_BUF_TRANSLATION / MI_BUF_ROTATION / MI_BUF_SCALE (mi_device_buffer).
+ * Cost (profiles/r10_animation/ab.md, one run, wall clock): mi_anim_frame + mi_propagate for 1 000 rigs x 24 joints on one shared
+ * clip 26 us, 40 000 rigs 95 us; numpy sampling on a core + mi_upload_transforms_indexed + mi_propagate 1.5 ms and 47 ms (0.44 and
+ * 2.5 ms of that are upload + propagate).  The kernel alone, cubic tracks, tracks too long for LDS and scattered rows: not measured.
+ * Per target the launch reads 20 bytes of target, up to three 16-byte track descriptors and two keys' values per track, and writes
+ * 40 bytes of Transform and one change byte. */
+#define MI_ANIM_NO_TRACK 0xFFFFFFFFu
+#define MI_ANIM_STEP 0x0u
+#define MI_ANIM_LINEAR 0x1u
+#define MI_ANIM_CUBIC 0x2u
+#define MI_ANIM_TRANSLATION 0x00u
+#define MI_ANIM_ROTATION 0x10u
+#define MI_ANIM_SCALE 0x20u
+typedef struct mi_anim_track {
+    uint32_t first_time, n_keys;  /* times[first_time, first_time + n_keys) */
+    uint32_t first_value;         /* values[first_value ..]: n_keys x (3 or 4) floats, x 3 for MI_ANIM_CUBIC */
+    uint32_t kind_interp;         /* MI_ANIM_TRANSLATION / _ROTATION / _SCALE | MI_ANIM_STEP / _LINEAR / _CUBIC */
+} mi_anim_track;
+typedef struct mi_anim_target {
+    uint32_t row, player;                /* the row written; the index of its player's seek time */
+    uint32_t track_t, track_r, track_s;  /* indices into the track pool, or MI_ANIM_NO_TRACK */
+} mi_anim_target;
+int32_t mi_anim_upload_tracks(mi_ctx* ctx, uint32_t n_tracks, const mi_anim_track* tracks, uint32_t n_times, const float* times, uint32_t n_values,
+                              const float* values);
+int32_t mi_anim_upload_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_target* targets);
+int32_t mi_anim_frame(mi_ctx* ctx, uint32_t n_players, const float* seek_time, uint32_t flags);
+
+/* ======================================================================================= */
 /* camera helpers (pure host code; what update_frusta computes, visibility/mod.rs:627-636)   */
 /* ======================================================================================= */
 
@@ -983,6 +1054,9 @@ int32_t mi_exchange_download(mi_ctx* ctx, void* out_host, uint64_t bytes);
 #define MI_BUF_BATCH_SETS_INDEXED 11
 #define MI_BUF_JOINT_MATRICES 12          /* 64 bytes per slot; these two swap under MI_SKIN_KEEP_PREVIOUS and are valid until the next mi_skin_upload */
 #define MI_BUF_JOINT_MATRICES_PREVIOUS 13
+#define MI_BUF_TRANSLATION 14             /* the Transform columns: 12 / 16 / 12 bytes per row; valid until the next mi_columns_resize */
+#define MI_BUF_ROTATION 15
+#define MI_BUF_SCALE 16
 int32_t mi_device_buffer(mi_ctx* ctx, uint32_t which, void** out_device_ptr, uint64_t* out_bytes);
 
 /* Bench / test instrumentation (HIP-event timers, the per-kernel profile, planner and trace hooks) is declared in

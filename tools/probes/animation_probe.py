@@ -1,0 +1,128 @@
+"""profiles/r10_animation/ab.md: mi_anim_frame + mi_propagate against host sampling + mi_upload_transforms_indexed + mi_propagate,
+N rigs x 24 joints, one shared clip (linear tracks, 30 keys, one player per rig); and the deviation of a float32 numpy run of the
+test's reference from its float64 run on the test's own inputs (no GPU needed for that part: --deviation).
+    python tools/probes/animation_probe.py [--deviation] [--rigs 1000,40000] [--reps 30]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import bevy_amd as B  # noqa: E402
+
+F32, U32 = np.float32, np.uint32
+JOINTS, KEYS = 24, 30
+
+
+def deviation():
+    import test_gpu_animation as T
+    worst = {"translation / scale, in units of the bound": 0.0, "rotation, in units of 2^-24": 0.0}
+    for n_targets, interp, k, layout in T.CASES:
+        rng = np.random.default_rng(1000 * n_targets + 100 * interp + k)
+        per = T.build(rng, n_targets, n_targets + 40, interp, k, layout)[4]
+        for x in T.SEEKS:
+            for tv in per:
+                for c in range(3):
+                    if tv[c] is None:
+                        continue
+                    v64, bound = T.sample(*tv[c], c == 1, interp, F32(x))
+                    v32 = T.sample(*tv[c], c == 1, interp, F32(x), F32)[0]
+                    if np.all(np.asarray(bound) == 0):
+                        assert np.array_equal(v32, v64)
+                    elif c == 1:
+                        worst["rotation, in units of 2^-24"] = max(worst["rotation, in units of 2^-24"], np.max(np.abs(v32 - v64)) / T.E)
+                    else:
+                        key = "translation / scale, in units of the bound"
+                        worst[key] = max(worst[key], np.max(np.abs(v32 - v64) / bound))
+    for k, v in worst.items():
+        print(f"float32 numpy against float64, test inputs, worst {k}: {v:.2f}")
+
+
+def clip(rng):
+    """One clip: 24 joints x (t, r, s) linear tracks over one range of KEYS times."""
+    times = np.linspace(0, 1, KEYS).astype(F32)
+    tracks, values, n_v = np.zeros(3 * JOINTS, B.ANIM_TRACK_DTYPE), [], 0
+    for j in range(JOINTS):
+        for c, (comp, w) in enumerate(((B.ANIM_TRANSLATION, 3), (B.ANIM_ROTATION, 4), (B.ANIM_SCALE, 3))):
+            v = rng.normal(0, 1, (KEYS, w))
+            if c == 1:
+                v /= np.linalg.norm(v, axis=1, keepdims=True)
+            tracks[3 * j + c] = (0, KEYS, n_v, comp | B.ANIM_LINEAR)
+            values.append(v.astype(F32).reshape(-1))
+            n_v += v.size
+    return tracks, times, np.concatenate(values)
+
+
+def host_sample(times, vals, x):
+    """numpy sampling of the clip for every rig: vals [JOINTS][3] of [KEYS, w]; x [rigs] -> t [rigs * JOINTS, 3], r, s (nlerp-free
+    slerp left out: the host path is charged the cheaper lerp + normalize for rotations)"""
+    i = np.clip(np.searchsorted(times, x, side="right") - 1, 0, KEYS - 2)
+    u = ((x - times[i]) / (times[i + 1] - times[i])).astype(F32)[:, None, None]
+    out = []
+    for c in range(3):
+        v = vals[c]  # [JOINTS, KEYS, w]
+        a, b = v[:, i].transpose(1, 0, 2), v[:, i + 1].transpose(1, 0, 2)
+        o = a + (b - a) * u
+        if c == 1:
+            o /= np.linalg.norm(o, axis=2, keepdims=True)
+        out.append(o.reshape(-1, o.shape[2]).astype(F32))
+    return out
+
+
+def quartiles(xs):
+    q = np.percentile(np.array(xs) * 1e6, [25, 50, 75])
+    return f"{q[1]:.1f} us (quartiles {q[0]:.1f} - {q[2]:.1f})"
+
+
+def ab(rigs, reps):
+    rng = np.random.default_rng(rigs)
+    tracks, times, values = clip(rng)
+    n = rigs * JOINTS
+    targets = np.zeros(n, B.ANIM_TARGET_DTYPE)
+    targets["row"], targets["player"] = np.arange(n), np.arange(n) // JOINTS
+    for c, f in enumerate(("track_t", "track_r", "track_s")):
+        targets[f] = 3 * (np.arange(n) % JOINTS) + c
+    vals = [np.stack([values[tracks[3 * j + c]["first_value"]:][:KEYS * w].reshape(KEYS, w) for j in range(JOINTS)]) for c, w in enumerate((3, 4, 3))]
+    rows = np.arange(n, dtype=U32)
+    dev, host, host_sampling = [], [], []
+    with B.Context() as ctx:
+        ctx.resize(n)
+        ctx.upload_transforms(np.zeros(3 * n, F32), np.tile(np.array([0, 0, 0, 1], F32), n), np.ones(3 * n, F32))
+        ctx.propagate()
+        ctx.anim_upload_tracks(tracks, times, values)
+        ctx.anim_upload_targets(targets)
+        for rep in range(reps + 5):  # (five warm-up frames)
+            x = rng.uniform(0.01, 0.99, rigs).astype(F32)
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            ctx.anim_frame(x)
+            ctx.propagate(0)
+            ctx.synchronize()
+            t1 = time.perf_counter()
+            t, r, s = host_sample(times, vals, x)
+            t2 = time.perf_counter()
+            ctx.upload_transforms_indexed(rows, t.reshape(-1), r.reshape(-1), s.reshape(-1))
+            ctx.propagate(0)
+            ctx.synchronize()
+            t3 = time.perf_counter()
+            if rep >= 5:
+                dev.append(t1 - t0), host.append(t3 - t1), host_sampling.append(t2 - t1)
+    print(f"{rigs} rigs x {JOINTS} joints, {reps} frames, wall clock around synchronize:")
+    print(f"  anim_frame + propagate                                   {quartiles(dev)}")
+    print(f"  numpy sampling + upload_transforms_indexed + propagate   {quartiles(host)}  (the sampling alone {quartiles(host_sampling)})")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--deviation", action="store_true")
+    ap.add_argument("--rigs", default="1000,40000")
+    ap.add_argument("--reps", type=int, default=30)
+    a = ap.parse_args()
+    if a.deviation:
+        deviation()
+    else:
+        for rigs in a.rigs.split(","):
+            ab(int(rigs), a.reps)
