@@ -39,6 +39,20 @@ def deviation():
                         worst[key] = max(worst[key], np.max(np.abs(v32 - v64) / bound))
     for k, v in worst.items():
         print(f"float32 numpy against float64, test inputs, worst {k}: {v:.2f}")
+    # the cases of the search seams, seek-time edges and many players: the float32 run has to stay inside the test's own bounds
+    worst = 0.0
+    for name, (fn, *args) in T.NEW_CASES.items():
+        case = fn(*args)
+        cur = [np.zeros((case["n"], w), F32) for w in (3, 4, 3)]
+        for seeks in case["seeks"]:
+            (w64, bound), (w32, _) = [T.expected(cur, case["targets"], case["per"], seeks, dt=dt) for dt in (np.float64, F32)]
+            for c in range(3):
+                exact = bound[c] == 0
+                assert np.array_equal(w32[c][exact], w64[c][exact]), (name, c)
+                ratio = np.max(np.abs(w32[c] - w64[c])[~exact] / bound[c][~exact], initial=0.0)
+                assert ratio <= 1, (name, c, ratio)
+                worst = max(worst, ratio)
+    print(f"float32 numpy against float64, the {len(T.NEW_CASES)} later cases, worst error / bound: {worst:.2f}")
 
 
 def clip(rng):
