@@ -6,8 +6,12 @@ bench.py use to reach the C ABI from Python (ctypes).  There is NO CPU fallback:
 point needs a gfx950 device and raises `MiError` otherwise.
 """
 from .api import (  # noqa: F401
+    ANIM_BINDING_DTYPE,
+    ANIM_BLEND_TARGET_DTYPE,
     ANIM_CUBIC,
+    ANIM_LAYER_DTYPE,
     ANIM_LINEAR,
+    ANIM_MAX_LAYERS,
     ANIM_NO_TRACK,
     ANIM_ROTATION,
     ANIM_SCALE,

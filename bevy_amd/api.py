@@ -194,6 +194,10 @@ ANIM_STEP, ANIM_LINEAR, ANIM_CUBIC = 0x0, 0x1, 0x2
 ANIM_TRANSLATION, ANIM_ROTATION, ANIM_SCALE = 0x00, 0x10, 0x20
 ANIM_TRACK_DTYPE = np.dtype([("first_time", np.uint32), ("n_keys", np.uint32), ("first_value", np.uint32), ("kind_interp", np.uint32)])  # mi_anim_track
 ANIM_TARGET_DTYPE = np.dtype([("row", np.uint32), ("player", np.uint32), ("track_t", np.uint32), ("track_r", np.uint32), ("track_s", np.uint32)])  # mi_anim_target
+ANIM_MAX_LAYERS = 8
+ANIM_BINDING_DTYPE = np.dtype([("track_t", np.uint32), ("track_r", np.uint32), ("track_s", np.uint32)])  # mi_anim_binding
+ANIM_BLEND_TARGET_DTYPE = np.dtype([("row", np.uint32), ("player", np.uint32), ("first_binding", np.uint32), ("n_clips", np.uint32)])  # mi_anim_blend_target
+ANIM_LAYER_DTYPE = np.dtype([("player", np.uint32), ("clip", np.uint32), ("seek_time", np.float32), ("weight", np.float32)])  # mi_anim_layer
 
 ABI_SYMBOLS = [
     "mi_abi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_last_error_string", "mi_synchronize",
@@ -211,7 +215,7 @@ ABI_SYMBOLS = [
     "mi_cluster_assign_frame",
     "mi_batch_upload_rows", "mi_batch_upload_sets", "mi_batch_upload_row_bins", "mi_batch_upload_bins", "mi_batch_build", "mi_batch_build_phase",
     "mi_batch_sorted_build", "mi_upload_depth_bias", "mi_phase_sort", "mi_phase_sort_download", "mi_skin_upload_inverse_bindposes", "mi_skin_upload", "mi_skin_frame", "mi_skin_download_matrices", "mi_skin_download_bounds",
-    "mi_anim_upload_tracks", "mi_anim_upload_targets", "mi_anim_frame",
+    "mi_anim_upload_tracks", "mi_anim_upload_targets", "mi_anim_frame", "mi_anim_upload_blend_targets", "mi_anim_frame_blended",
     "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
     "mi_bind_visibility_output", "mi_exchange_set_mode", "mi_exchange_configure", "mi_exchange_configure_multi", "mi_exchange_configure_owned", "mi_exchange_group_flush", "mi_exchange_last", "mi_exchange_download", "mi_device_buffer",
 ]
@@ -887,6 +891,20 @@ class Context:
         """Before propagate: every target's Transform from its tracks at seek_times[player] (f32, one per player)."""
         st = _f32(seek_times).reshape(-1)
         self._ck(self._lib.mi_anim_frame(self._h, len(st), _ptr(st, C.c_float) if len(st) else None, C.c_uint32(0)))
+
+    def anim_upload_blend_targets(self, targets, bindings):
+        """targets: ANIM_BLEND_TARGET_DTYPE[n] (the row written, its player, its range of `bindings`); bindings: ANIM_BINDING_DTYPE[m],
+        bindings[first_binding + c] = the tracks clip slot c of the player's graph animates on that row (or ANIM_NO_TRACK)."""
+        tg = np.ascontiguousarray(targets, ANIM_BLEND_TARGET_DTYPE).reshape(-1)
+        bd = np.ascontiguousarray(bindings, ANIM_BINDING_DTYPE).reshape(-1)
+        self._ck(self._lib.mi_anim_upload_blend_targets(self._h, len(tg), tg.ctypes.data_as(C.c_void_p) if len(tg) else None, len(bd),
+                                                        bd.ctypes.data_as(C.c_void_p) if len(bd) else None))
+
+    def anim_frame_blended(self, n_players, layers):
+        """Before propagate: every blended target's Transform from its player's layers (ANIM_LAYER_DTYPE[n], grouped by player in
+        ascending order; the order inside a player is the blend order; layers of weight <= 0 or NaN are dropped)."""
+        ly = np.ascontiguousarray(layers, ANIM_LAYER_DTYPE).reshape(-1)
+        self._ck(self._lib.mi_anim_frame_blended(self._h, int(n_players), len(ly), ly.ctypes.data_as(C.c_void_p) if len(ly) else None, C.c_uint32(0)))
 
     def batch_download(self):
         """-> dict: work_items / metadata / batch_sets (lists indexed by mesh class, u32 arrays), records u32[k, 8], unbatchable

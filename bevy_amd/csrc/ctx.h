@@ -374,6 +374,12 @@ struct mi_ctx {
     uint32_t an_player_end = 0;   // highest player any target names, + 1
     uint32_t an_scale_lo = 0, an_scale_hi = 0;  // the rows of the targets with a scale track lie in [lo, hi] (an_any_scale)
     bool an_have_tracks = false, an_have_targets = false, an_any_scale = false;
+    // ... the blended targets (mi_anim_upload_blend_targets), a state of their own beside the single-clip targets, over the same pool
+    DevBuf an_bl_targets, an_bl_bindings, an_bl_wg_times;  // the layouts: kernels.h, AnimBlendArgs
+    std::vector<uint32_t> an_bl_players, an_bl_clips, an_bl_count;  // the players that have targets, ascending; the smallest n_clips of each one's targets; how many it has
+    uint32_t an_bl_n_targets = 0, an_bl_row_end = 0, an_bl_player_end = 0;  // (as the three above)
+    uint32_t an_bl_scale_lo = 0, an_bl_scale_hi = 0;  // the rows whose bindings hold any scale track lie in [lo, hi] (an_bl_any_scale)
+    bool an_have_blend_targets = false, an_bl_any_scale = false;
     DevBuf cl_remap, cl_bind_oc, cl_bind_idx, cl_block_counts, cl_pair_cb, cl_pair_mask, cl_acc, cl_offsets, cl_indices, cl_scalars;
     // derive mode of an assignment that runs in or next to the frame kernel: which rows that frame's propagate writes (cull_frame sets them)
     const uint8_t* cl_derive_changed = nullptr;

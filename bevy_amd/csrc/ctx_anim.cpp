@@ -1,6 +1,7 @@
 // ctx_anim.cpp -- animation clips: the entry points in front of kernels_anim.hip.  The two uploads check every index the kernel
 // will follow (it tests none of them again) and lay the targets out for it; mi_anim_frame is one launch, and to the context's state
-// what an indexed Transform upload of the same rows is (indexed_write_begin / _end, context.cpp).
+// what an indexed Transform upload of the same rows is (indexed_write_begin / _end, context.cpp).  The same pair for blended
+// players: mi_anim_upload_blend_targets and mi_anim_frame_blended, which also checks and packs the frame's layers.
 #include "ctx.h"
 
 using namespace mi;
@@ -37,12 +38,12 @@ int32_t mi_anim_upload_tracks(mi_ctx* ctx, uint32_t n_tracks, const mi_anim_trac
     if ((rc = ensure(ctx, ctx->an_tracks, (size_t)n_tracks * sizeof(mi_anim_track)))) return rc;
     if ((rc = ensure(ctx, ctx->an_times, (size_t)n_times * 4))) return rc;
     if ((rc = ensure(ctx, ctx->an_values, (size_t)n_values * 4))) return rc;
-    ctx->an_have_tracks = ctx->an_have_targets = false;
+    ctx->an_have_tracks = ctx->an_have_targets = ctx->an_have_blend_targets = false;
     if ((rc = upload(ctx, ctx->an_tracks.p, tracks, (size_t)n_tracks * sizeof(mi_anim_track)))) return rc;
     if ((rc = upload(ctx, ctx->an_times.p, times, (size_t)n_times * 4))) return rc;
     if ((rc = upload(ctx, ctx->an_values.p, values, (size_t)n_values * 4))) return rc;
     ctx->an_tracks_host.assign(tracks, tracks + n_tracks);
-    ctx->an_n_targets = 0;
+    ctx->an_n_targets = ctx->an_bl_n_targets = 0;
     ctx->an_have_tracks = true;
     return MI_OK;
 }
@@ -147,6 +148,176 @@ int32_t mi_anim_frame(mi_ctx* ctx, uint32_t n_players, const float* seek_time, u
     a.anc = w.anc;
     HIP_TRY(ctx, launch_anim_frame(a, ctx->stream));
     indexed_write_end(ctx, w, ctx->an_n_targets);
+    return MI_OK;
+}
+
+int32_t mi_anim_upload_blend_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_blend_target* targets, uint32_t n_bindings, const mi_anim_binding* bindings) {
+    ENTER(ctx);
+    if ((n_targets && !targets) || (n_bindings && !bindings)) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: NULL array");
+    if (!ctx->an_have_tracks) return fail(ctx, MI_ERR_NOT_READY, "mi_anim_upload_blend_targets before mi_anim_upload_tracks");
+    // ---- validation: nothing of the previous blended targets is touched before it has passed ----
+    const std::vector<mi_anim_track>& pool = ctx->an_tracks_host;
+    static const char* const field[3] = {"track_t", "track_r", "track_s"};
+    static const uint32_t comp_of[3] = {ANIM_TRANSLATION, ANIM_ROTATION, ANIM_SCALE};
+    uint32_t row_end = 0, player_end = 0, scale_lo = 0xFFFFFFFFu, scale_hi = 0;
+    for (uint32_t i = 0; i < n_targets; ++i) {
+        const mi_anim_blend_target& tg = targets[i];
+        if (tg.row >= ctx->n) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: target %u: row %u >= %u live rows", i, tg.row, ctx->n);
+        if (tg.player == 0xFFFFFFFFu) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: target %u: player 0x%x", i, tg.player);
+        if (tg.n_clips == 0) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: target %u has no clips", i);
+        if ((uint64_t)tg.first_binding + tg.n_clips > n_bindings)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: target %u: bindings [%u,+%u) exceed %u", i, tg.first_binding, tg.n_clips, n_bindings);
+        for (uint32_t c = 0; c < tg.n_clips; ++c) {
+            const mi_anim_binding& bd = bindings[tg.first_binding + c];
+            const uint32_t tr[3] = {bd.track_t, bd.track_r, bd.track_s};
+            for (uint32_t k = 0; k < 3; ++k) {
+                if (tr[k] == MI_ANIM_NO_TRACK) continue;
+                if (tr[k] >= pool.size())
+                    return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: target %u, clip %u: %s %u >= %zu tracks", i, c, field[k], tr[k], pool.size());
+                if ((pool[tr[k]].kind_interp & ~ANIM_INTERP_MASK) != comp_of[k])
+                    return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: target %u, clip %u: %s %u is a track of another component (kind_interp 0x%x)", i, c,
+                                field[k], tr[k], pool[tr[k]].kind_interp);
+            }
+            if (bd.track_s != MI_ANIM_NO_TRACK) scale_lo = std::min(scale_lo, tg.row), scale_hi = std::max(scale_hi, tg.row);
+        }
+        row_end = std::max(row_end, tg.row + 1u);
+        player_end = std::max(player_end, tg.player + 1u);
+    }
+    // ---- the launch order, as mi_anim_upload_targets: by player, by row ----
+    std::vector<uint32_t> order(n_targets);
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return targets[x].row < targets[y].row; });
+    for (uint32_t i = 1; i < n_targets; ++i)
+        if (targets[order[i]].row == targets[order[i - 1u]].row)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: row %u belongs to two targets", targets[order[i]].row);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return targets[x].player < targets[y].player; });
+    // ---- per player: its targets [g0, g1) of the order, the smallest n_clips among them, and its block of the re-laid bindings
+    // ---- (kernels.h, AnimBlendArgs: [clip][component][target of the player])
+    std::vector<uint32_t> players, clips, count, soa((size_t)4 * n_targets), relaid;
+    std::vector<uint32_t> reach(n_targets);  // the clips of a target a layer can name: its player's smallest n_clips
+    for (uint32_t g0 = 0, g1; g0 < n_targets; g0 = g1) {
+        const uint32_t player = targets[order[g0]].player;
+        uint32_t c_min = 0xFFFFFFFFu;
+        for (g1 = g0; g1 < n_targets && targets[order[g1]].player == player; ++g1) c_min = std::min(c_min, targets[order[g1]].n_clips);
+        const uint32_t t_n = g1 - g0;
+        const uint64_t block = relaid.size();
+        if (block + (uint64_t)3 * c_min * t_n > 0xFFFFFFFFull) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_blend_targets: more than 2^32 binding words");
+        relaid.resize((size_t)(block + (uint64_t)3 * c_min * t_n));
+        for (uint32_t j = 0; j < t_n; ++j) {
+            const mi_anim_blend_target& tg = targets[order[g0 + j]];
+            const uint32_t col[4] = {tg.row, tg.player, (uint32_t)block + j, t_n};
+            for (uint32_t c = 0; c < 4; ++c) soa[(size_t)c * n_targets + g0 + j] = col[c];
+            reach[g0 + j] = c_min;
+            for (uint32_t c = 0; c < c_min; ++c) {
+                const mi_anim_binding& bd = bindings[tg.first_binding + c];
+                const uint32_t tr[3] = {bd.track_t, bd.track_r, bd.track_s};
+                for (uint32_t k = 0; k < 3; ++k) relaid[(size_t)block + (size_t)(3u * c + k) * t_n + j] = tr[k];
+            }
+        }
+        players.push_back(player), clips.push_back(c_min), count.push_back(t_n);
+    }
+    const uint32_t n_wgs = (n_targets + ANIM_BLEND_TARGETS - 1u) / ANIM_BLEND_TARGETS;
+    std::vector<uint32_t> wg_times((size_t)2 * n_wgs, 0u);
+    for (uint32_t w = 0; w < n_wgs; ++w) {
+        uint64_t lo = UINT64_MAX, hi = 0;  // the range of key times the tracks within this workgroup's reach use
+        for (uint32_t i = w * ANIM_BLEND_TARGETS; i < std::min(n_targets, (w + 1u) * ANIM_BLEND_TARGETS); ++i)
+            for (uint32_t e = 0; e < 3u * reach[i]; ++e) {
+                const uint32_t tr = relaid[(size_t)soa[(size_t)2 * n_targets + i] + (size_t)e * soa[(size_t)3 * n_targets + i]];
+                if (tr == MI_ANIM_NO_TRACK) continue;
+                lo = std::min<uint64_t>(lo, pool[tr].first_time);
+                hi = std::max<uint64_t>(hi, (uint64_t)pool[tr].first_time + pool[tr].n_keys);
+            }
+        if (lo < hi && hi - lo <= ANIM_LDS_TIMES) wg_times[2u * w] = (uint32_t)lo, wg_times[2u * w + 1u] = (uint32_t)(hi - lo);
+    }
+    int32_t rc;
+    if ((rc = ensure(ctx, ctx->an_bl_targets, soa.size() * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_bl_bindings, relaid.size() * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_bl_wg_times, wg_times.size() * 4))) return rc;
+    ctx->an_have_blend_targets = false;
+    if ((rc = upload(ctx, ctx->an_bl_targets.p, soa.data(), soa.size() * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_bl_bindings.p, relaid.data(), relaid.size() * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_bl_wg_times.p, wg_times.data(), wg_times.size() * 4))) return rc;
+    ctx->an_bl_players.swap(players), ctx->an_bl_clips.swap(clips), ctx->an_bl_count.swap(count);
+    ctx->an_bl_n_targets = n_targets;
+    ctx->an_bl_row_end = row_end;
+    ctx->an_bl_player_end = player_end;
+    ctx->an_bl_any_scale = scale_lo <= scale_hi;
+    ctx->an_bl_scale_lo = ctx->an_bl_any_scale ? scale_lo : 0u;
+    ctx->an_bl_scale_hi = scale_hi;
+    ctx->an_have_blend_targets = true;
+    return MI_OK;
+}
+
+int32_t mi_anim_frame_blended(mi_ctx* ctx, uint32_t n_players, uint32_t n_layers, const mi_anim_layer* layers, uint32_t flags) {
+    ENTER(ctx);
+    if (flags) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: flags 0x%x", flags);
+    if (!ctx->an_have_tracks || !ctx->an_have_blend_targets)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_frame_blended before mi_anim_upload_tracks and mi_anim_upload_blend_targets");
+    if (ctx->an_bl_row_end > ctx->n)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_frame_blended: the targets write row %u, the context has %u rows (upload the targets again)", ctx->an_bl_row_end - 1u,
+                    ctx->n);
+    if (ctx->an_bl_player_end > n_players)
+        return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: a target names player %u, n_players = %u", ctx->an_bl_player_end - 1u, n_players);
+    if (n_layers && !layers) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: NULL");
+    // ---- the layers the kernel will see: weight > 0, of players that have targets (an_bl_players ascends, as the layers' players must)
+    std::vector<uint32_t> kept;
+    const std::vector<uint32_t>& players = ctx->an_bl_players;
+    size_t cur = 0;
+    uint32_t of_player = 0, rows = 0;  // kept layers of players[cur] so far; targets of the players with kept layers
+    for (uint32_t i = 0; i < n_layers; ++i) {
+        const mi_anim_layer& ly = layers[i];
+        if (i && ly.player < layers[i - 1u].player)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: layer %u: player %u behind player %u (layers go by player, ascending)", i, ly.player, layers[i - 1u].player);
+        if (ly.player >= n_players) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: layer %u: player %u >= n_players = %u", i, ly.player, n_players);
+        if (!(ly.weight > 0.0f)) continue;  // (zero, negative, NaN)
+        while (cur < players.size() && players[cur] < ly.player) ++cur, of_player = 0;
+        if (cur == players.size() || players[cur] != ly.player) continue;  // (a player without blended targets: nothing to write)
+        if (ly.clip >= ctx->an_bl_clips[cur])
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: layer %u: clip %u, a target of player %u has %u clips", i, ly.clip, ly.player, ctx->an_bl_clips[cur]);
+        if (++of_player > MI_ANIM_MAX_LAYERS)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: player %u has more than %u layers of weight > 0", ly.player, MI_ANIM_MAX_LAYERS);
+        if (of_player == 1u) rows += ctx->an_bl_count[cur];
+        kept.push_back(i);
+    }
+    if (kept.empty()) return MI_OK;  // every player is left alone
+    if (kept.size() >> ANIM_BLEND_COUNT_SHIFT) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_blended: %zu layers", kept.size());
+    // ---- one word per player and 12 bytes per kept layer, in the pinned staging block: the kernel reads them where they are ----
+    void *st = nullptr, *d_st = nullptr;
+    int32_t rc = stage_alloc(ctx, ((size_t)n_players + 3u * kept.size()) * 4, &st);
+    if (rc) return rc;
+    uint32_t *words = (uint32_t*)st, *packed = words + n_players;
+    memset(words, 0, (size_t)n_players * 4);
+    for (size_t k = 0; k < kept.size(); ++k) {
+        const mi_anim_layer& ly = layers[kept[k]];
+        if (!words[ly.player]) words[ly.player] = (uint32_t)k;
+        words[ly.player] += 1u << ANIM_BLEND_COUNT_SHIFT;
+        packed[3u * k] = ly.clip;
+        memcpy(packed + 3u * k + 1u, &ly.seek_time, 8);  // seek_time, weight
+    }
+    HIP_TRY(ctx, hipHostGetDevicePointer(&d_st, st, 0));
+    IndexedWrite w{};
+    if ((rc = indexed_write_begin(ctx, &w))) return rc;
+    if (ctx->an_bl_any_scale) row_summary_touch(ctx, ROWSUM_PART_SCALE, ctx->an_bl_scale_lo, ctx->an_bl_scale_hi - ctx->an_bl_scale_lo + 1u);
+    AnimBlendArgs a{};
+    a.n_targets = ctx->an_bl_n_targets;
+    a.targets = (const uint32_t*)ctx->an_bl_targets.p;
+    a.bindings = (const uint32_t*)ctx->an_bl_bindings.p;
+    a.wg_times = (const uint32_t*)ctx->an_bl_wg_times.p;
+    a.tracks = (const uint32_t*)ctx->an_tracks.p;
+    a.times = (const float*)ctx->an_times.p;
+    a.values = (const float*)ctx->an_values.p;
+    a.players = (const uint32_t*)d_st;
+    a.layers = (const uint32_t*)d_st + n_players;
+    a.t = ctx->t, a.r = ctx->r, a.s = ctx->s;
+    a.changed = ctx->changed;
+    a.changed_gen = ctx->changed_gen;
+    a.parent_idx = w.parent_idx;
+    a.mark_bytes = w.mark_cur;
+    a.clear_words = w.clear_other;
+    a.n_clear_words = w.n_clear_words;
+    a.anc = w.anc;
+    HIP_TRY(ctx, launch_anim_blend(a, ctx->stream));
+    indexed_write_end(ctx, w, rows);
     return MI_OK;
 }
 

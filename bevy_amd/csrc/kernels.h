@@ -876,4 +876,40 @@ struct AnimArgs {
 };
 hipError_t launch_anim_frame(AnimArgs a, hipStream_t stream);
 
+// One launch per mi_anim_frame_blended: 256 threads own 64 consecutive targets (in the order mi_anim_upload_blend_targets laid them
+// out: by player, by row); wave w samples layer 4 r + w of its lanes' players in round r, and behind a barrier waves 0 / 1 / 2 fold
+// the translations / rotations / scales of the round's four layers, wave 3 stamps and marks the rows (kernels_anim.hip).
+// Layouts (every index checked on the host, none again here):
+//   targets    four columns of n_targets words: row, player, bind0, bind_stride
+//   bindings   per player one block of C x 3 x T words, C = the smallest n_clips of its T targets (no layer may name a clip beyond
+//              it): the track of clip c, component k (0 t, 1 r, 2 s), of the player's j-th target (by row) is
+//              bindings[block + (3 c + k) T + j].  bind0 = block + j and bind_stride = T are the target's two columns: for a fixed
+//              clip and component the consecutive targets of a player read consecutive words.
+//   players    one word per player, in the pinned staging block: first kept layer | kept layers << 28 (0 = the player is left alone)
+//   layers     three words per kept layer, behind them: clip, seek time, weight (> 0)
+constexpr uint32_t ANIM_BLEND_TARGETS = 64u, ANIM_BLEND_WAVES = 4u, ANIM_MAX_LAYERS = 8u;  // MI_ANIM_MAX_LAYERS (public header)
+constexpr uint32_t ANIM_BLEND_COLS = 12u;  // the tile's columns per layer: t 0-2, r 3-6, s 7-9, weight 10, has-mask 11 (bit k: component k)
+constexpr uint32_t ANIM_BLEND_COUNT_SHIFT = 28u;
+struct AnimBlendArgs {
+    uint32_t n_targets;
+    uint32_t n_target_wgs;       // as AnimArgs
+    const uint32_t* targets;
+    const uint32_t* bindings;
+    const uint32_t* wg_times;    // as AnimArgs, per workgroup of 64 targets: over every track of the bindings its targets can reach
+    const uint32_t* tracks;
+    const float* times;
+    const float* values;
+    const uint32_t* players;     // [n_players], pinned host memory mapped into the device
+    const uint32_t* layers;      // [kept layers] x 3, the same block
+    float *t, *r, *s;
+    uint8_t* changed;
+    uint32_t changed_gen;
+    const uint32_t* parent_idx;  // as AnimArgs
+    uint8_t* mark_bytes;
+    uint32_t* clear_words;
+    uint32_t n_clear_words;
+    const uint32_t* anc;
+};
+hipError_t launch_anim_blend(AnimBlendArgs a, hipStream_t stream);
+
 }  // namespace mi

@@ -18,6 +18,7 @@
 //             when the launch is also the frame's mark_dirty_trees (as k_upload_trs_indexed, kernels_flat.hip), marks the row and
 //             its ancestors; the launch zeroes the other half of the marks when asked to.
 // Arithmetic: glam_math.h (every operation rounded on its own; -ffp-contract=off); acosf / sinf are the device library's.
+// Behind k_anim_frame: k_anim_blend, the same sampling for players that blend several weighted clips (mi_anim_frame_blended).
 #include "glam_math.h"
 #include "kernels.h"
 
@@ -205,7 +206,141 @@ __global__ __launch_bounds__(ANIM_THREADS) void k_anim_frame(AnimArgs a) {
         anim_targets<false>(a, AnimTimes<false>{a.times, lds_times, 0u}, gid);
     }
 }
+// ---- blended players (mi_anim_frame_blended; kernels.h, AnimBlendArgs) ---------------------------------------------------------
+// 256 threads own 64 consecutive targets; lane j of every wave is target j.  In round r wave w samples layer 4 r + w of its lanes'
+// players -- the targets are sorted by player and the four waves differ in the layer, not in the targets, so a wave holds one clip at
+// one seek time as a rule and anim_sample finds the key interval once for it -- and leaves ten floats, the weight and a has-mask per
+// lane in its quarter of a layer-major LDS tile [4][ANIM_BLEND_COLS][64] (lanes are consecutive words of a column: no bank
+// conflicts).  Behind the barrier the fold is split by component: wave 0 folds the translations of the round's four layers in order,
+// wave 1 the rotations (the slerp chain), wave 2 the scales, each carrying its accumulator and weight sum in registers across the
+// rounds; wave 3 stamps and marks the rows in front of the first round.  The rounds: ceil(most kept layers of the 64 targets / 4), the
+// same in every wave without an exchange (all four read the same 64 players).  A second barrier closes a round before the tile is
+// written again.  After the last round waves 0 - 2 store one column each.
+
+// One component of the round's four layers folded into (acc, wsum), in layer order: the first contributing layer is taken as it
+// is; a later one moves acc by u = weight / (the weights so far + weight).
+template <int W, bool ROT>
+__device__ __forceinline__ void anim_fold(const float* tile, uint32_t col0, uint32_t bit, uint32_t lane, AnimVal<W>& acc, float& wsum, bool& any) {
+#pragma unroll
+    for (uint32_t l = 0; l < ANIM_BLEND_WAVES; ++l) {
+        const float* c = tile + l * (ANIM_BLEND_COLS * 64u) + lane;
+        if (!((__float_as_uint(c[11u * 64u]) >> bit) & 1u)) continue;  // (a wave whose lane has no such layer wrote mask 0)
+        AnimVal<W> v;
+#pragma unroll
+        for (int e = 0; e < W; ++e) v.v[e] = c[(col0 + e) * 64u];
+        const float weight = c[10u * 64u];
+        if (!any) {
+            acc = v, wsum = weight, any = true;
+            continue;
+        }
+        wsum = wsum + weight;
+        const float u = f_div(weight, wsum);
+        if constexpr (ROT) {
+            const V4 q = anim_slerp(V4{acc.v[0], acc.v[1], acc.v[2], acc.v[3]}, V4{v.v[0], v.v[1], v.v[2], v.v[3]}, u);
+            acc.v[0] = q.x, acc.v[1] = q.y, acc.v[2] = q.z, acc.v[3] = q.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e) acc.v[e] = acc.v[e] + (v.v[e] - acc.v[e]) * u;
+        }
+    }
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void anim_blend_targets(const AnimBlendArgs& b, const AnimTimes<STAGED>& ts, float* tile) {
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    const uint32_t gid = blockIdx.x * ANIM_BLEND_TARGETS + lane;
+    uint32_t row = 0, bind0 = 0, stride = 0, first = 0, count = 0;  // count = 0: past the targets, or a player without kept layers
+    if (gid < b.n_targets) {
+        const size_t n = b.n_targets;
+        const uint32_t* tg = b.targets + gid;
+        const uint32_t pw = b.players[tg[n]];
+        row = tg[0], bind0 = tg[2u * n], stride = tg[3u * n];
+        first = pw & ((1u << ANIM_BLEND_COUNT_SHIFT) - 1u), count = pw >> ANIM_BLEND_COUNT_SHIFT;
+    }
+    if (wave == 3u && count) {
+        b.changed[row] = (uint8_t)b.changed_gen;
+        if (b.mark_bytes) mark_row_and_ancestors(row, b.parent_idx, b.mark_bytes, b.anc, 0xFFFFu);
+    }
+    AnimArgs a{};  // what anim_sample reads of it: the two pools
+    a.tracks = b.tracks, a.values = b.values;
+    AnimVal<4> acc{};  // waves 0 and 2 use three of the four
+    float wsum = 0.0f;
+    bool any = false;
+    for (uint32_t r = 0; __ballot(count > ANIM_BLEND_WAVES * r) != 0; ++r) {  // (the same trips in all four waves)
+        const uint32_t l = ANIM_BLEND_WAVES * r + wave;
+        const bool on = l < count;
+        uint32_t track_t = ANIM_NO_TRACK, track_r = ANIM_NO_TRACK, track_s = ANIM_NO_TRACK;
+        float x = 0.0f, weight = 0.0f;
+        if (on) {
+            const uint32_t* ly = b.layers + 3ull * (first + l);
+            const uint32_t* bd = b.bindings + ((size_t)bind0 + (size_t)(3u * ly[0]) * stride);
+            x = __uint_as_float(ly[1]), weight = __uint_as_float(ly[2]);
+            track_t = bd[0], track_r = bd[stride], track_s = bd[2u * (size_t)stride];
+        }
+        AnimVal<3> vt{}, vs{};
+        AnimVal<4> vr{};
+        const bool has_t = anim_sample<3, false>(a, ts, track_t, on, x, lane, vt);
+        const bool has_r = anim_sample<4, true>(a, ts, track_r, on, x, lane, vr);
+        const bool has_s = anim_sample<3, false>(a, ts, track_s, on, x, lane, vs);
+        float* c = tile + wave * (ANIM_BLEND_COLS * 64u) + lane;
+        c[0u * 64u] = vt.v[0], c[1u * 64u] = vt.v[1], c[2u * 64u] = vt.v[2];
+        c[3u * 64u] = vr.v[0], c[4u * 64u] = vr.v[1], c[5u * 64u] = vr.v[2], c[6u * 64u] = vr.v[3];
+        c[7u * 64u] = vs.v[0], c[8u * 64u] = vs.v[1], c[9u * 64u] = vs.v[2];
+        c[10u * 64u] = weight;
+        c[11u * 64u] = __uint_as_float((has_t ? 1u : 0u) | (has_r ? 2u : 0u) | (has_s ? 4u : 0u));
+        __syncthreads();
+        if (wave == 0u) {
+            AnimVal<3> v3{{acc.v[0], acc.v[1], acc.v[2]}};
+            anim_fold<3, false>(tile, 0u, 0u, lane, v3, wsum, any);
+            acc.v[0] = v3.v[0], acc.v[1] = v3.v[1], acc.v[2] = v3.v[2];
+        } else if (wave == 1u) {
+            anim_fold<4, true>(tile, 3u, 1u, lane, acc, wsum, any);
+        } else if (wave == 2u) {
+            AnimVal<3> v3{{acc.v[0], acc.v[1], acc.v[2]}};
+            anim_fold<3, false>(tile, 7u, 2u, lane, v3, wsum, any);
+            acc.v[0] = v3.v[0], acc.v[1] = v3.v[1], acc.v[2] = v3.v[2];
+        }
+        __syncthreads();
+    }
+    if (!any) return;  // (wave 3; a lane without a contributing layer: the component is not written)
+    if (wave == 1u) {
+        reinterpret_cast<float4*>(b.r)[row] = make_float4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+    } else {
+        float* o = (wave == 0u ? b.t : b.s) + 3ull * row;
+        o[0] = acc.v[0], o[1] = acc.v[1], o[2] = acc.v[2];
+    }
+}
+
+__global__ __launch_bounds__(ANIM_BLEND_TARGETS* ANIM_BLEND_WAVES) void k_anim_blend(AnimBlendArgs b) {
+    constexpr uint32_t THREADS = ANIM_BLEND_TARGETS * ANIM_BLEND_WAVES;
+    __shared__ float lds_times[ANIM_LDS_TIMES];
+    __shared__ float tile[ANIM_BLEND_WAVES * ANIM_BLEND_COLS * 64u];
+    if (b.clear_words)
+        for (uint32_t w = blockIdx.x * THREADS + threadIdx.x; w < b.n_clear_words; w += gridDim.x * THREADS) b.clear_words[w] = 0u;
+    if (blockIdx.x >= b.n_target_wgs) return;  // (whole workgroups)
+    const uint32_t lo = b.wg_times[2u * blockIdx.x], n = b.wg_times[2u * blockIdx.x + 1u];  // (n <= ANIM_LDS_TIMES: the upload saw to it)
+    if (n) {  // (workgroup-uniform)
+        for (uint32_t j = threadIdx.x; j < n; j += THREADS) lds_times[j] = b.times[lo + j];
+        __syncthreads();
+        anim_blend_targets<true>(b, AnimTimes<true>{b.times, lds_times, lo}, tile);
+    } else {
+        anim_blend_targets<false>(b, AnimTimes<false>{b.times, lds_times, 0u}, tile);
+    }
+}
 }  // namespace
+
+hipError_t launch_anim_blend(AnimBlendArgs a, hipStream_t stream) {
+    if (a.n_targets == 0) return hipSuccess;
+    a.n_target_wgs = (a.n_targets + ANIM_BLEND_TARGETS - 1u) / ANIM_BLEND_TARGETS;
+    uint32_t grid = a.n_target_wgs;
+    if (a.clear_words) {  // (as launch_anim_frame)
+        const uint32_t cb = (a.n_clear_words + 1023u) / 1024u < 1024u ? (a.n_clear_words + 1023u) / 1024u : 1024u;
+        grid = grid > cb ? grid : cb;
+    }
+    if (!a.mark_bytes) a.anc = nullptr;
+    MI_LAUNCH(k_anim_blend, dim3(grid), dim3(ANIM_BLEND_TARGETS * ANIM_BLEND_WAVES), 0, stream, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_anim_frame(AnimArgs a, hipStream_t stream) {
     if (a.n_targets == 0) return hipSuccess;

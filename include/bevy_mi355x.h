@@ -877,8 +877,10 @@ int32_t mi_skin_download_bounds(mi_ctx* ctx, uint32_t first_skin, uint32_t n, fl
 /* The stage in front of mi_propagate for animated rigs: what animate_targets (bevy_animation) writes into the Transform of every
  * animation target of a player that plays ONE clip at weight 1, computed on the device from a resident pool of keyframe tracks and
  * one float per player -- its seek time -- instead of being sampled on a core and uploaded, 40 bytes per joint and frame.
- * Out of scope: blend graphs, transitions between clips, morph weights, and advancing the players' clocks.  The host advances
- * seek_time per player and keeps the stock system for blended players.
+ * Players that blend one level of weighted clips -- a transition's crossfade, a flat blend node over clip nodes -- go through
+ * mi_anim_upload_blend_targets / mi_anim_frame_blended below.  Out of scope: nested blend nodes, additive nodes and masks, morph
+ * weights, and advancing the players' clocks.  The host advances the seek times and the weights, and keeps the stock system for
+ * players whose graph is more than one level of weighted clips.
  * The reference sources were not at hand when this was written: the arithmetic stated here is the library's definition, in glam's
  * operation order as everywhere else, and has NOT been pinned against a run of the reference.
  *
@@ -941,6 +943,56 @@ int32_t mi_anim_upload_tracks(mi_ctx* ctx, uint32_t n_tracks, const mi_anim_trac
                               const float* values);
 int32_t mi_anim_upload_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_target* targets);
 int32_t mi_anim_frame(mi_ctx* ctx, uint32_t n_players, const float* seek_time, uint32_t flags);
+
+/* Blended players: several (clip, seek time, weight) layers per player and frame, each sampled by the rules above and folded in
+ * order by cumulative weight -- what a flat blend node over clip nodes does (AnimationGraph::from_clips, AnimationTransitions).
+ *
+ *   mi_anim_upload_blend_targets  replaces the blended targets, a state of their own beside mi_anim_upload_targets' over the same
+ *                    track pool (mi_anim_upload_tracks drops both).  A target writes row `row` for player `player`;
+ *                    bindings[first_binding + c], c < n_clips, names the tracks clip slot c of the player's graph animates on
+ *                    that row (MI_ANIM_NO_TRACK: that clip leaves the component alone).  Checked, MI_ERR_INVALID_ARG with a
+ *                    message and the previous state left in place: rows below the row count and distinct; binding ranges
+ *                    inside the array; n_clips >= 1; track indices in range and of the matching component.  The library
+ *                    reorders the targets (by player, by row) and keeps per player the smallest n_clips of its targets.
+ *   mi_anim_frame_blended  one kernel launch, asynchronous; call it before mi_propagate.  layers: grouped by player in
+ *                    non-descending player order (else MI_ERR_INVALID_ARG); the order inside a player is the blend order.
+ *                    Layers whose weight is not > 0 (zero, negative, NaN) are dropped on the host, as are layers of a player
+ *                    without blended targets.  MI_ERR_INVALID_ARG with a message: a layer's player >= n_players; a target's
+ *                    player >= n_players; a kept layer's clip >= the smallest n_clips of its player's targets; more than
+ *                    MI_ANIM_MAX_LAYERS kept layers of one player.  MI_ERR_NOT_READY as mi_anim_frame.  flags: pass 0.
+ *                    A player without a kept layer is left alone: its rows are neither written nor stamped.  For the rows of
+ *                    every other player the call is the twin of mi_upload_transforms_indexed, as mi_anim_frame is.
+ * The blend, per component (translation, rotation, scale) separately, every operation rounded on its own: take the player's kept
+ * layers in order and skip those whose binding has MI_ANIM_NO_TRACK for the component; v = the layer's track sampled at its
+ * seek_time by the rules above.
+ *     first contributing layer   acc = v, W = weight
+ *     every later one            W = W + weight, u = weight / W;
+ *                                translation, scale: acc = acc + (v - acc) * u per component
+ *                                rotation: acc = slerp(acc, v, u) -- the slerp above, sign flip and 0.9995 branch included
+ * A component no layer contributes to is not written; the row's change byte is stamped all the same (as for a target without
+ * tracks).  A player with exactly one kept layer gets, bit for bit, what mi_anim_frame writes for the same tracks and seek time,
+ * whatever the weight.  The library's definition, like the sampling: not pinned against a run of the reference.
+ * Per frame one word per player and 12 bytes per kept layer travel in the pinned staging block; no copy is launched in front.
+ * Cost (profiles/r11_blend/ab.md, one run, wall clock): mi_anim_frame_blended + mi_propagate for 1 000 rigs x 24 joints crossfading
+ * two shared clips 43 us, 40 000 rigs 458 us; numpy sampling and blending on a core + mi_upload_transforms_indexed + mi_propagate
+ * 2.8 ms and 115 ms.  With ONE layer the kernel takes 1.5 to 3.5 times what mi_anim_frame's does on the same work (four waves per
+ * 64 targets against one): keep unblended players on mi_anim_frame.  Not measured: scattered rows, tracks too long for LDS
+ * (DESIGN.md 4.10). */
+#define MI_ANIM_MAX_LAYERS 8u
+typedef struct mi_anim_binding {
+    uint32_t track_t, track_r, track_s;  /* one clip's tracks for one target, or MI_ANIM_NO_TRACK */
+} mi_anim_binding;
+typedef struct mi_anim_blend_target {
+    uint32_t row, player;
+    uint32_t first_binding, n_clips;  /* bindings[first_binding + c], c < n_clips: what clip slot c animates on this row */
+} mi_anim_blend_target;
+typedef struct mi_anim_layer {
+    uint32_t player, clip;
+    float seek_time, weight;
+} mi_anim_layer;
+int32_t mi_anim_upload_blend_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_blend_target* targets, uint32_t n_bindings,
+                                     const mi_anim_binding* bindings);
+int32_t mi_anim_frame_blended(mi_ctx* ctx, uint32_t n_players, uint32_t n_layers, const mi_anim_layer* layers, uint32_t flags);
 
 /* ======================================================================================= */
 /* camera helpers (pure host code; what update_frusta computes, visibility/mod.rs:627-636)   */

@@ -1,7 +1,10 @@
 """profiles/r10_animation/ab.md: mi_anim_frame + mi_propagate against host sampling + mi_upload_transforms_indexed + mi_propagate,
 N rigs x 24 joints, one shared clip (linear tracks, 30 keys, one player per rig); and the deviation of a float32 numpy run of the
 test's reference from its float64 run on the test's own inputs (no GPU needed for that part: --deviation).
-    python tools/probes/animation_probe.py [--deviation] [--rigs 1000,40000] [--reps 30]"""
+    python tools/probes/animation_probe.py [--deviation] [--rigs 1000,40000] [--reps 30]
+profiles/r11_blend/ab.md: --blend, the crossfade scene -- every rig's player with two layers of a shared pair of clips at weights 0.3 /
+0.7 through mi_anim_frame_blended, the same with one layer beside mi_anim_frame on identical work, and the host path (numpy sampling
+and blending + mi_upload_transforms_indexed); --blend-deviation, the float32 run of test_gpu_anim_blend's reference (no GPU needed)."""
 import argparse
 import os
 import sys
@@ -129,14 +132,101 @@ def ab(rigs, reps):
     print(f"  numpy sampling + upload_transforms_indexed + propagate   {quartiles(host)}  (the sampling alone {quartiles(host_sampling)})")
 
 
+def blend_deviation():
+    import test_gpu_anim_blend as T
+    rot, lerp = 0.0, 0.0
+    for n, L in T.CASES:
+        sc = T.blend_scene(n, L)
+        (w64, bound), (w32, _) = [T.expected(sc, sc["cur"], dt) for dt in (np.float64, F32)]
+        for c in range(3):
+            exact, err = bound[c] == 0, np.abs(w32[c] - w64[c])
+            assert np.array_equal(w32[c][exact], w64[c][exact]), (n, L, c)
+            if c == 1:
+                rot = max(rot, np.max(err[bound[c] == T.ROT_BOUND], initial=0.0) / T.E)
+            else:
+                lerp = max(lerp, np.max(err[~exact] / bound[c][~exact], initial=0.0))
+    print(f"float32 numpy against float64 over the {len(T.CASES)} blend cases: blended rotations worst {rot:.2f} x 2^-24 (the test's bound: "
+          f"{T.ROT_BOUND / T.E:.0f}), translation / scale worst error / bound {lerp:.2f}")
+
+
+def blend_ab(rigs, reps):
+    """Two clips over the same 24 joints; a rig's 24 targets share the 24 x 2 bindings with every other rig."""
+    rng = np.random.default_rng(rigs)
+    clips = [clip(rng) for _ in range(2)]
+    tracks = np.concatenate([c[0] for c in clips])
+    tracks["first_time"][3 * JOINTS:] += KEYS
+    tracks["first_value"][3 * JOINTS:] += len(clips[0][2])
+    times, values = np.concatenate([c[1] for c in clips]), np.concatenate([c[2] for c in clips])
+    n = rigs * JOINTS
+    single = np.zeros(n, B.ANIM_TARGET_DTYPE)
+    single["row"], single["player"] = np.arange(n), np.arange(n) // JOINTS
+    bindings = np.zeros(2 * JOINTS, B.ANIM_BINDING_DTYPE)
+    for c, f in enumerate(("track_t", "track_r", "track_s")):
+        single[f] = 3 * (np.arange(n) % JOINTS) + c
+        bindings[f] = 3 * JOINTS * (np.arange(2 * JOINTS) % 2) + 3 * (np.arange(2 * JOINTS) // 2) + c
+    targets = np.zeros(n, B.ANIM_BLEND_TARGET_DTYPE)
+    targets["row"], targets["player"], targets["first_binding"], targets["n_clips"] = np.arange(n), np.arange(n) // JOINTS, 2 * (np.arange(n) % JOINTS), 2
+    vals = [[np.stack([c[2][c[0][3 * j + k]["first_value"]:][:KEYS * w].reshape(KEYS, w) for j in range(JOINTS)]) for k, w in enumerate((3, 4, 3))] for c in clips]
+    two, one = np.zeros(2 * rigs, B.ANIM_LAYER_DTYPE), np.zeros(rigs, B.ANIM_LAYER_DTYPE)
+    two["player"], two["clip"], two["weight"] = np.arange(2 * rigs) // 2, np.arange(2 * rigs) % 2, np.tile(np.array([0.3, 0.7], F32), rigs)
+    one["player"], one["weight"] = np.arange(rigs), 1.0
+    rows = np.arange(n, dtype=U32)
+    took = {k: [] for k in ("two", "one", "frame", "host", "host sampling")}
+    with B.Context() as ctx:
+        ctx.resize(n)
+        ctx.upload_transforms(np.zeros(3 * n, F32), np.tile(np.array([0, 0, 0, 1], F32), n), np.ones(3 * n, F32))
+        ctx.propagate()
+        ctx.anim_upload_tracks(tracks, times, values)
+        ctx.anim_upload_targets(single)
+        ctx.anim_upload_blend_targets(targets, bindings)
+
+        def timed(key, fn, keep):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ctx.propagate(0)
+            ctx.synchronize()
+            if keep:
+                took[key].append(time.perf_counter() - t0)
+
+        def host_path(x, keep):
+            t0 = time.perf_counter()
+            a, b = host_sample(clips[0][1], vals[0], x[0::2]), host_sample(clips[1][1], vals[1], x[1::2])
+            t, r, s = [p + (q - p) * F32(0.7) for p, q in zip(a, b)]  # (u = 0.7 / (0.3 + 0.7); rotations: the cheaper nlerp, no sign flip)
+            r /= np.linalg.norm(r, axis=1, keepdims=True)
+            if keep:
+                took["host sampling"].append(time.perf_counter() - t0)
+            ctx.upload_transforms_indexed(rows, t.reshape(-1), r.reshape(-1), s.reshape(-1))
+
+        for rep in range(reps + 5):  # (five warm-up frames; the four paths alternate)
+            two["seek_time"] = rng.uniform(0.01, 0.99, 2 * rigs)
+            one["seek_time"] = two["seek_time"][0::2]
+            timed("two", lambda: ctx.anim_frame_blended(rigs, two), rep >= 5)
+            timed("one", lambda: ctx.anim_frame_blended(rigs, one), rep >= 5)
+            timed("frame", lambda: ctx.anim_frame(one["seek_time"]), rep >= 5)
+            timed("host", lambda: host_path(two["seek_time"], rep >= 5), rep >= 5)
+    print(f"{rigs} rigs x {JOINTS} joints, {reps} frames, wall clock around synchronize:")
+    print(f"  anim_frame_blended, two layers (0.3 / 0.7) + propagate             {quartiles(took['two'])}")
+    print(f"  anim_frame_blended, one layer + propagate                          {quartiles(took['one'])}")
+    print(f"  anim_frame (the same tracks and seek times) + propagate            {quartiles(took['frame'])}")
+    print(f"  numpy sampling and blending + upload_transforms_indexed + propagate {quartiles(took['host'])}  (sampling and blending alone {quartiles(took['host sampling'])})")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--deviation", action="store_true")
     ap.add_argument("--rigs", default="1000,40000")
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--blend", action="store_true")
+    ap.add_argument("--blend-deviation", action="store_true")
     a = ap.parse_args()
     if a.deviation:
         deviation()
+    elif a.blend_deviation:
+        blend_deviation()
+    elif a.blend:
+        for rigs in a.rigs.split(","):
+            blend_ab(int(rigs), a.reps)
     else:
         for rigs in a.rigs.split(","):
             ab(int(rigs), a.reps)
