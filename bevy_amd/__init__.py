@@ -9,9 +9,19 @@ from .api import (  # noqa: F401
     ANIM_BINDING_DTYPE,
     ANIM_BLEND_TARGET_DTYPE,
     ANIM_CUBIC,
+    ANIM_GRAPH_DTYPE,
+    ANIM_GRAPH_NODE_DTYPE,
+    ANIM_GRAPH_TARGET_DTYPE,
     ANIM_LAYER_DTYPE,
     ANIM_LINEAR,
+    ANIM_MAX_GRAPH_DEPTH,
+    ANIM_MAX_GRAPH_NODES,
     ANIM_MAX_LAYERS,
+    ANIM_NODE_ADD,
+    ANIM_NODE_BLEND,
+    ANIM_NODE_CLIP,
+    ANIM_NODE_STATE_DTYPE,
+    ANIM_NO_NODE,
     ANIM_NO_TRACK,
     ANIM_ROTATION,
     ANIM_SCALE,

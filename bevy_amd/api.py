@@ -198,6 +198,14 @@ ANIM_MAX_LAYERS = 8
 ANIM_BINDING_DTYPE = np.dtype([("track_t", np.uint32), ("track_r", np.uint32), ("track_s", np.uint32)])  # mi_anim_binding
 ANIM_BLEND_TARGET_DTYPE = np.dtype([("row", np.uint32), ("player", np.uint32), ("first_binding", np.uint32), ("n_clips", np.uint32)])  # mi_anim_blend_target
 ANIM_LAYER_DTYPE = np.dtype([("player", np.uint32), ("clip", np.uint32), ("seek_time", np.float32), ("weight", np.float32)])  # mi_anim_layer
+ANIM_NODE_CLIP, ANIM_NODE_BLEND, ANIM_NODE_ADD = 0, 1, 2
+ANIM_NO_NODE = 0xFFFFFFFF
+ANIM_MAX_GRAPH_DEPTH, ANIM_MAX_GRAPH_NODES = 8, 64
+ANIM_GRAPH_NODE_DTYPE = np.dtype([("kind", np.uint32), ("parent", np.uint32), ("clip", np.uint32), ("mask_lo", np.uint32), ("mask_hi", np.uint32)])  # mi_anim_graph_node
+ANIM_GRAPH_DTYPE = np.dtype([("first_node", np.uint32), ("n_nodes", np.uint32)])  # mi_anim_graph
+ANIM_GRAPH_TARGET_DTYPE = np.dtype([("row", np.uint32), ("player", np.uint32), ("first_binding", np.uint32), ("n_clips", np.uint32), ("groups_lo", np.uint32),
+                                    ("groups_hi", np.uint32)])  # mi_anim_graph_target
+ANIM_NODE_STATE_DTYPE = np.dtype([("weight", np.float32), ("seek_time", np.float32)])  # mi_anim_node_state
 
 ABI_SYMBOLS = [
     "mi_abi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_last_error_string", "mi_synchronize",
@@ -216,6 +224,7 @@ ABI_SYMBOLS = [
     "mi_batch_upload_rows", "mi_batch_upload_sets", "mi_batch_upload_row_bins", "mi_batch_upload_bins", "mi_batch_build", "mi_batch_build_phase",
     "mi_batch_sorted_build", "mi_upload_depth_bias", "mi_phase_sort", "mi_phase_sort_download", "mi_skin_upload_inverse_bindposes", "mi_skin_upload", "mi_skin_frame", "mi_skin_download_matrices", "mi_skin_download_bounds",
     "mi_anim_upload_tracks", "mi_anim_upload_targets", "mi_anim_frame", "mi_anim_upload_blend_targets", "mi_anim_frame_blended",
+    "mi_anim_upload_graphs", "mi_anim_upload_graph_targets", "mi_anim_frame_graph",
     "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
     "mi_bind_visibility_output", "mi_exchange_set_mode", "mi_exchange_configure", "mi_exchange_configure_multi", "mi_exchange_configure_owned", "mi_exchange_group_flush", "mi_exchange_last", "mi_exchange_download", "mi_device_buffer",
 ]
@@ -905,6 +914,32 @@ class Context:
         ascending order; the order inside a player is the blend order; layers of weight <= 0 or NaN are dropped)."""
         ly = np.ascontiguousarray(layers, ANIM_LAYER_DTYPE).reshape(-1)
         self._ck(self._lib.mi_anim_frame_blended(self._h, int(n_players), len(ly), ly.ctypes.data_as(C.c_void_p) if len(ly) else None, C.c_uint32(0)))
+
+    def anim_upload_graphs(self, graphs, nodes):
+        """Replaces all animation graphs (and drops the graph targets).  graphs: ANIM_GRAPH_DTYPE[n], each a range of `nodes`
+        (ANIM_GRAPH_NODE_DTYPE[m]: kind ANIM_NODE_CLIP / _BLEND / _ADD, parent within the graph or ANIM_NO_NODE, clip slot, own mask)."""
+        gr = np.ascontiguousarray(graphs, ANIM_GRAPH_DTYPE).reshape(-1)
+        nd = np.ascontiguousarray(nodes, ANIM_GRAPH_NODE_DTYPE).reshape(-1)
+        self._ck(self._lib.mi_anim_upload_graphs(self._h, len(gr), gr.ctypes.data_as(C.c_void_p) if len(gr) else None, len(nd),
+                                                 nd.ctypes.data_as(C.c_void_p) if len(nd) else None))
+
+    def anim_upload_graph_targets(self, targets, bindings, player_graph):
+        """targets: ANIM_GRAPH_TARGET_DTYPE[n] (as the blend targets, plus the target's mask groups); bindings: ANIM_BINDING_DTYPE[m];
+        player_graph: u32 per player, the graph it runs or ANIM_NO_NODE."""
+        tg = np.ascontiguousarray(targets, ANIM_GRAPH_TARGET_DTYPE).reshape(-1)
+        bd = np.ascontiguousarray(bindings, ANIM_BINDING_DTYPE).reshape(-1)
+        pg = np.ascontiguousarray(player_graph, np.uint32).reshape(-1)
+        self._ck(self._lib.mi_anim_upload_graph_targets(self._h, len(tg), tg.ctypes.data_as(C.c_void_p) if len(tg) else None, len(bd),
+                                                        bd.ctypes.data_as(C.c_void_p) if len(bd) else None, len(pg),
+                                                        pg.ctypes.data_as(C.c_void_p) if len(pg) else None))
+
+    def anim_frame_graph(self, first_state, states):
+        """Before propagate: every graph target's Transform from its player's graph.  first_state: u32 per player, where its nodes'
+        states begin in `states` (ANIM_NODE_STATE_DTYPE[n]: weight, seek time, in node order), or ANIM_NO_NODE = left alone."""
+        fs = np.ascontiguousarray(first_state, np.uint32).reshape(-1)
+        st = np.ascontiguousarray(states, ANIM_NODE_STATE_DTYPE).reshape(-1)
+        self._ck(self._lib.mi_anim_frame_graph(self._h, len(fs), fs.ctypes.data_as(C.c_void_p) if len(fs) else None, len(st),
+                                               st.ctypes.data_as(C.c_void_p) if len(st) else None, C.c_uint32(0)))
 
     def batch_download(self):
         """-> dict: work_items / metadata / batch_sets (lists indexed by mesh class, u32 arrays), records u32[k, 8], unbatchable

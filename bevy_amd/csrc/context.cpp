@@ -1030,7 +1030,7 @@ int32_t mi_ctx_destroy(mi_ctx* ctx) {
                       &ctx->cl_offsets, &ctx->cl_indices, &ctx->cl_scalars, &ctx->ps_pairs[0], &ctx->ps_pairs[1], &ctx->ps_table, &ctx->ps_rows,
                       &ctx->ps_keys, &ctx->ps_dist, &ctx->ps_count, &ctx->sk_pool, &ctx->sk_joint_rows, &ctx->sk_slot_bind, &ctx->sk_bounded, &ctx->sk_aabbs,
                       &ctx->sk_bounds, &ctx->sk_mats[0], &ctx->sk_mats[1], &ctx->an_tracks, &ctx->an_times, &ctx->an_values, &ctx->an_targets, &ctx->an_wg_times,
-                      &ctx->an_bl_targets, &ctx->an_bl_bindings, &ctx->an_bl_wg_times};
+                      &ctx->an_bl_targets, &ctx->an_bl_bindings, &ctx->an_bl_wg_times, &ctx->an_gr_prog, &ctx->an_gr_targets, &ctx->an_gr_bindings, &ctx->an_gr_wg};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& sl : ctx->cl_parked)  // (the parked cluster views' buffers; the selected one's are in the list above)

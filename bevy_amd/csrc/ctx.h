@@ -380,6 +380,15 @@ struct mi_ctx {
     uint32_t an_bl_n_targets = 0, an_bl_row_end = 0, an_bl_player_end = 0;  // (as the three above)
     uint32_t an_bl_scale_lo = 0, an_bl_scale_hi = 0;  // the rows whose bindings hold any scale track lie in [lo, hi] (an_bl_any_scale)
     bool an_have_blend_targets = false, an_bl_any_scale = false;
+    // ... animation graphs (mi_anim_upload_graphs) and their targets (mi_anim_upload_graph_targets), a third state over the same pool
+    DevBuf an_gr_prog, an_gr_targets, an_gr_bindings, an_gr_wg;  // the layouts: kernels.h, AnimGraphArgs
+    std::vector<mi_anim_graph> an_gr_graphs;       // the last upload's graphs and nodes (the targets' upload checks clips against them)
+    std::vector<mi_anim_graph_node> an_gr_nodes;
+    std::vector<uint32_t> an_gr_prog_first, an_gr_prog_n;  // per graph: its instructions in an_gr_prog
+    std::vector<uint32_t> an_gr_player_graph, an_gr_player_count;  // per player: its graph (or MI_ANIM_NO_NODE); how many targets it has
+    uint32_t an_gr_n_targets = 0, an_gr_row_end = 0, an_gr_player_end = 0;  // (n_targets: padding included; the other two as above)
+    uint32_t an_gr_scale_lo = 0, an_gr_scale_hi = 0;
+    bool an_have_graphs = false, an_have_graph_targets = false, an_gr_any_scale = false;
     DevBuf cl_remap, cl_bind_oc, cl_bind_idx, cl_block_counts, cl_pair_cb, cl_pair_mask, cl_acc, cl_offsets, cl_indices, cl_scalars;
     // derive mode of an assignment that runs in or next to the frame kernel: which rows that frame's propagate writes (cull_frame sets them)
     const uint8_t* cl_derive_changed = nullptr;

@@ -1,7 +1,9 @@
 // ctx_anim.cpp -- animation clips: the entry points in front of kernels_anim.hip.  The two uploads check every index the kernel
 // will follow (it tests none of them again) and lay the targets out for it; mi_anim_frame is one launch, and to the context's state
 // what an indexed Transform upload of the same rows is (indexed_write_begin / _end, context.cpp).  The same pair for blended
-// players: mi_anim_upload_blend_targets and mi_anim_frame_blended, which also checks and packs the frame's layers.
+// players: mi_anim_upload_blend_targets and mi_anim_frame_blended, which also checks and packs the frame's layers.  And a triple
+// for whole animation graphs: mi_anim_upload_graphs compiles each tree into the program k_anim_graph runs, mi_anim_upload_graph_targets
+// lays the targets out by graph, mi_anim_frame_graph hands the frame's node states over.
 #include "ctx.h"
 
 using namespace mi;
@@ -38,12 +40,12 @@ int32_t mi_anim_upload_tracks(mi_ctx* ctx, uint32_t n_tracks, const mi_anim_trac
     if ((rc = ensure(ctx, ctx->an_tracks, (size_t)n_tracks * sizeof(mi_anim_track)))) return rc;
     if ((rc = ensure(ctx, ctx->an_times, (size_t)n_times * 4))) return rc;
     if ((rc = ensure(ctx, ctx->an_values, (size_t)n_values * 4))) return rc;
-    ctx->an_have_tracks = ctx->an_have_targets = ctx->an_have_blend_targets = false;
+    ctx->an_have_tracks = ctx->an_have_targets = ctx->an_have_blend_targets = ctx->an_have_graph_targets = false;
     if ((rc = upload(ctx, ctx->an_tracks.p, tracks, (size_t)n_tracks * sizeof(mi_anim_track)))) return rc;
     if ((rc = upload(ctx, ctx->an_times.p, times, (size_t)n_times * 4))) return rc;
     if ((rc = upload(ctx, ctx->an_values.p, values, (size_t)n_values * 4))) return rc;
     ctx->an_tracks_host.assign(tracks, tracks + n_tracks);
-    ctx->an_n_targets = ctx->an_bl_n_targets = 0;
+    ctx->an_n_targets = ctx->an_bl_n_targets = ctx->an_gr_n_targets = 0;
     ctx->an_have_tracks = true;
     return MI_OK;
 }
@@ -317,6 +319,254 @@ int32_t mi_anim_frame_blended(mi_ctx* ctx, uint32_t n_players, uint32_t n_layers
     a.n_clear_words = w.n_clear_words;
     a.anc = w.anc;
     HIP_TRY(ctx, launch_anim_blend(a, ctx->stream));
+    indexed_write_end(ctx, w, rows);
+    return MI_OK;
+}
+
+int32_t mi_anim_upload_graphs(mi_ctx* ctx, uint32_t n_graphs, const mi_anim_graph* graphs, uint32_t n_nodes, const mi_anim_graph_node* nodes) {
+    ENTER(ctx);
+    if ((n_graphs && !graphs) || (n_nodes && !nodes)) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: NULL array");
+    // ---- validation and compilation: nothing of the previous graphs is touched before every graph has passed ----
+    std::vector<uint32_t> prog, prog_first(n_graphs), prog_n(n_graphs);
+    for (uint32_t gi = 0; gi < n_graphs; ++gi) {
+        const mi_anim_graph& gr = graphs[gi];
+        if (gr.n_nodes == 0 || gr.n_nodes > MI_ANIM_MAX_GRAPH_NODES)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u has %u nodes (1 .. %u)", gi, gr.n_nodes, MI_ANIM_MAX_GRAPH_NODES);
+        if ((uint64_t)gr.first_node + gr.n_nodes > n_nodes)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u: nodes [%u,+%u) exceed %u", gi, gr.first_node, gr.n_nodes, n_nodes);
+        const mi_anim_graph_node* nd = nodes + gr.first_node;
+        uint32_t depth[ANIM_GRAPH_MAX_NODES];
+        uint64_t eff[ANIM_GRAPH_MAX_NODES];
+        std::vector<uint32_t> kids[ANIM_GRAPH_MAX_NODES];
+        for (uint32_t k = 0; k < gr.n_nodes; ++k) {
+            if (nd[k].kind > MI_ANIM_NODE_ADD) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u, node %u: unknown kind %u", gi, k, nd[k].kind);
+            const uint64_t own = (uint64_t)nd[k].mask_lo | (uint64_t)nd[k].mask_hi << 32;
+            if (k == 0) {
+                if (nd[0].parent != MI_ANIM_NO_NODE) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u: node 0 is the root, its parent is %u", gi, nd[0].parent);
+                depth[0] = 1u, eff[0] = own;
+                continue;
+            }
+            const uint32_t p = nd[k].parent;
+            if (p == MI_ANIM_NO_NODE) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u: node %u is a second root", gi, k);
+            if (p >= k) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u, node %u: parent %u is not below it", gi, k, p);
+            if (nd[p].kind == MI_ANIM_NODE_CLIP) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u, node %u: its parent %u is a clip node", gi, k, p);
+            depth[k] = depth[p] + 1u, eff[k] = own | eff[p];
+            if (depth[k] > MI_ANIM_MAX_GRAPH_DEPTH)
+                return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graphs: graph %u, node %u: depth %u (the root is 1, the most %u)", gi, k, depth[k], MI_ANIM_MAX_GRAPH_DEPTH);
+            kids[p].push_back(k);
+        }
+        // ---- the program (kernels.h, AnimGraphArgs): pre-order, children by ascending index; an inner node without children emits nothing
+        prog_first[gi] = (uint32_t)(prog.size() / 4u);
+        struct Open { uint32_t node, next, enter; };  // an entered inner node: its next child, and where its ENTER stands
+        std::vector<Open> open;
+        auto emit = [&](uint32_t op, uint32_t k, uint32_t clip) {
+            const uint32_t into = k ? nd[nd[k].parent].kind : (uint32_t)MI_ANIM_NODE_BLEND;  // (the root is the result's first and only child)
+            prog.insert(prog.end(), {op | depth[k] << 2 | into << 6 | k << 8, clip, (uint32_t)eff[k], (uint32_t)(eff[k] >> 32)});
+        };
+        auto visit = [&](uint32_t k) {
+            if (nd[k].kind == MI_ANIM_NODE_CLIP) emit(ANIM_OP_CLIP, k, nd[k].clip);
+            else if (!kids[k].empty()) open.push_back({k, 0u, (uint32_t)(prog.size() / 4u)}), emit(ANIM_OP_ENTER, k, 0u);
+        };
+        visit(0u);
+        while (!open.empty()) {
+            Open& o = open.back();
+            if (o.next < kids[o.node].size()) {
+                visit(kids[o.node][o.next++]);  // (may grow `open`: o is not used behind it)
+                continue;
+            }
+            emit(ANIM_OP_LEAVE, o.node, 0u);
+            prog[4u * (size_t)o.enter] |= ((uint32_t)(prog.size() / 4u) - o.enter) << 16;  // skip: to behind the LEAVE
+            open.pop_back();
+        }
+        prog_n[gi] = (uint32_t)(prog.size() / 4u) - prog_first[gi];
+    }
+    int32_t rc;
+    if ((rc = ensure(ctx, ctx->an_gr_prog, prog.size() * 4))) return rc;
+    ctx->an_have_graphs = ctx->an_have_graph_targets = false;
+    if ((rc = upload(ctx, ctx->an_gr_prog.p, prog.data(), prog.size() * 4))) return rc;
+    ctx->an_gr_graphs.assign(graphs, graphs + n_graphs);
+    ctx->an_gr_nodes.assign(nodes, nodes + n_nodes);
+    ctx->an_gr_prog_first.swap(prog_first), ctx->an_gr_prog_n.swap(prog_n);
+    ctx->an_gr_n_targets = 0;
+    ctx->an_have_graphs = true;
+    return MI_OK;
+}
+
+int32_t mi_anim_upload_graph_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_graph_target* targets, uint32_t n_bindings, const mi_anim_binding* bindings,
+                                     uint32_t n_players, const uint32_t* player_graph) {
+    ENTER(ctx);
+    if ((n_targets && !targets) || (n_bindings && !bindings) || (n_players && !player_graph))
+        return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: NULL array");
+    if (!ctx->an_have_tracks || !ctx->an_have_graphs)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_upload_graph_targets before mi_anim_upload_tracks and mi_anim_upload_graphs");
+    // ---- validation: nothing of the previous graph targets is touched before it has passed ----
+    const std::vector<mi_anim_track>& pool = ctx->an_tracks_host;
+    static const char* const field[3] = {"track_t", "track_r", "track_s"};
+    static const uint32_t comp_of[3] = {ANIM_TRANSLATION, ANIM_ROTATION, ANIM_SCALE};
+    for (uint32_t p = 0; p < n_players; ++p)
+        if (player_graph[p] != MI_ANIM_NO_NODE && player_graph[p] >= ctx->an_gr_graphs.size())
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: player %u: graph %u >= %zu graphs", p, player_graph[p], ctx->an_gr_graphs.size());
+    uint32_t row_end = 0, player_end = 0, scale_lo = 0xFFFFFFFFu, scale_hi = 0;
+    std::vector<uint32_t> c_min(n_players, 0xFFFFFFFFu), count(n_players, 0u);  // per player: the smallest n_clips of its targets; its targets
+    for (uint32_t i = 0; i < n_targets; ++i) {
+        const mi_anim_graph_target& tg = targets[i];
+        if (tg.row >= ctx->n) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: target %u: row %u >= %u live rows", i, tg.row, ctx->n);
+        if (tg.player >= n_players) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: target %u: player %u >= n_players = %u", i, tg.player, n_players);
+        if (player_graph[tg.player] == MI_ANIM_NO_NODE) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: target %u: player %u has no graph", i, tg.player);
+        if (tg.n_clips == 0) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: target %u has no clips", i);
+        if ((uint64_t)tg.first_binding + tg.n_clips > n_bindings)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: target %u: bindings [%u,+%u) exceed %u", i, tg.first_binding, tg.n_clips, n_bindings);
+        for (uint32_t c = 0; c < tg.n_clips; ++c) {
+            const mi_anim_binding& bd = bindings[tg.first_binding + c];
+            const uint32_t tr[3] = {bd.track_t, bd.track_r, bd.track_s};
+            for (uint32_t k = 0; k < 3; ++k) {
+                if (tr[k] == MI_ANIM_NO_TRACK) continue;
+                if (tr[k] >= pool.size())
+                    return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: target %u, clip %u: %s %u >= %zu tracks", i, c, field[k], tr[k], pool.size());
+                if ((pool[tr[k]].kind_interp & ~ANIM_INTERP_MASK) != comp_of[k])
+                    return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: target %u, clip %u: %s %u is a track of another component (kind_interp 0x%x)", i, c,
+                                field[k], tr[k], pool[tr[k]].kind_interp);
+            }
+            if (bd.track_s != MI_ANIM_NO_TRACK) scale_lo = std::min(scale_lo, tg.row), scale_hi = std::max(scale_hi, tg.row);
+        }
+        row_end = std::max(row_end, tg.row + 1u);
+        player_end = std::max(player_end, tg.player + 1u);
+        c_min[tg.player] = std::min(c_min[tg.player], tg.n_clips), ++count[tg.player];
+    }
+    for (uint32_t p = 0; p < n_players; ++p) {
+        if (!count[p]) continue;
+        const mi_anim_graph& gr = ctx->an_gr_graphs[player_graph[p]];
+        for (uint32_t k = 0; k < gr.n_nodes; ++k) {
+            const mi_anim_graph_node& nd = ctx->an_gr_nodes[gr.first_node + k];
+            if (nd.kind == MI_ANIM_NODE_CLIP && nd.clip >= c_min[p])
+                return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: graph %u, node %u: clip %u, a target of player %u has %u clips", player_graph[p], k, nd.clip, p,
+                            c_min[p]);
+        }
+    }
+    // ---- the launch order: by graph, by player, by row; a graph's targets start a workgroup of their own ----
+    std::vector<uint32_t> order(n_targets);
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return targets[x].row < targets[y].row; });
+    for (uint32_t i = 1; i < n_targets; ++i)
+        if (targets[order[i]].row == targets[order[i - 1u]].row)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: row %u belongs to two targets", targets[order[i]].row);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const mi_anim_graph_target &a = targets[x], &b = targets[y];
+        return player_graph[a.player] != player_graph[b.player] ? player_graph[a.player] < player_graph[b.player] : a.player < b.player;
+    });
+    std::vector<uint32_t> slot(n_targets);  // where target order[i] stands among the padded targets
+    uint64_t n_padded = 0;
+    for (uint32_t i = 0; i < n_targets; ++i) {
+        if (i && player_graph[targets[order[i]].player] != player_graph[targets[order[i - 1u]].player])
+            n_padded = (n_padded + ANIM_GRAPH_TARGETS - 1u) / ANIM_GRAPH_TARGETS * ANIM_GRAPH_TARGETS;
+        slot[i] = (uint32_t)n_padded++;
+    }
+    n_padded = (n_padded + ANIM_GRAPH_TARGETS - 1u) / ANIM_GRAPH_TARGETS * ANIM_GRAPH_TARGETS;
+    if (n_padded > 0x7FFFFFFFull) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: %u targets", n_targets);
+    const size_t np = (size_t)n_padded;
+    std::vector<uint32_t> soa(6 * np, 0u), relaid;
+    std::fill(soa.begin(), soa.begin() + np, ANIM_GRAPH_NO_NODE);  // (rows of the padding)
+    const uint32_t n_wgs = (uint32_t)(np / ANIM_GRAPH_TARGETS);
+    std::vector<uint32_t> wg((size_t)4 * n_wgs, 0u);
+    std::vector<uint64_t> t_lo(n_wgs, UINT64_MAX), t_hi(n_wgs, 0);  // per workgroup: the range of key times the tracks within its reach use
+    for (uint32_t g0 = 0, g1; g0 < n_targets; g0 = g1) {  // per player, as mi_anim_upload_blend_targets: its block of the re-laid bindings
+        const uint32_t player = targets[order[g0]].player, clips = c_min[player];
+        for (g1 = g0; g1 < n_targets && targets[order[g1]].player == player; ++g1) {}
+        const uint32_t t_n = g1 - g0;
+        const uint64_t block = relaid.size();
+        if (block + (uint64_t)3 * clips * t_n > 0xFFFFFFFFull) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_graph_targets: more than 2^32 binding words");
+        relaid.resize((size_t)(block + (uint64_t)3 * clips * t_n));
+        for (uint32_t j = 0; j < t_n; ++j) {
+            const mi_anim_graph_target& tg = targets[order[g0 + j]];
+            const uint32_t at = slot[g0 + j], w = at / ANIM_GRAPH_TARGETS;
+            const uint32_t col[6] = {tg.row, tg.player, (uint32_t)block + j, t_n, tg.groups_lo, tg.groups_hi};
+            for (uint32_t c = 0; c < 6; ++c) soa[c * np + at] = col[c];
+            wg[4u * w + 2u] = ctx->an_gr_prog_first[player_graph[player]], wg[4u * w + 3u] = ctx->an_gr_prog_n[player_graph[player]];
+            for (uint32_t c = 0; c < clips; ++c) {
+                const mi_anim_binding& bd = bindings[tg.first_binding + c];
+                const uint32_t tr[3] = {bd.track_t, bd.track_r, bd.track_s};
+                for (uint32_t k = 0; k < 3; ++k) {
+                    relaid[(size_t)block + (size_t)(3u * c + k) * t_n + j] = tr[k];
+                    if (tr[k] == MI_ANIM_NO_TRACK) continue;
+                    t_lo[w] = std::min<uint64_t>(t_lo[w], pool[tr[k]].first_time);
+                    t_hi[w] = std::max<uint64_t>(t_hi[w], (uint64_t)pool[tr[k]].first_time + pool[tr[k]].n_keys);
+                }
+            }
+        }
+    }
+    for (uint32_t w = 0; w < n_wgs; ++w)
+        if (t_lo[w] < t_hi[w] && t_hi[w] - t_lo[w] <= ANIM_LDS_TIMES) wg[4u * w] = (uint32_t)t_lo[w], wg[4u * w + 1u] = (uint32_t)(t_hi[w] - t_lo[w]);
+    int32_t rc;
+    if ((rc = ensure(ctx, ctx->an_gr_targets, soa.size() * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_gr_bindings, relaid.size() * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_gr_wg, wg.size() * 4))) return rc;
+    ctx->an_have_graph_targets = false;
+    if ((rc = upload(ctx, ctx->an_gr_targets.p, soa.data(), soa.size() * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_gr_bindings.p, relaid.data(), relaid.size() * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_gr_wg.p, wg.data(), wg.size() * 4))) return rc;
+    ctx->an_gr_player_graph.assign(player_graph, player_graph + n_players);
+    ctx->an_gr_player_count.swap(count);
+    ctx->an_gr_n_targets = (uint32_t)np;
+    ctx->an_gr_row_end = row_end;
+    ctx->an_gr_player_end = player_end;
+    ctx->an_gr_any_scale = scale_lo <= scale_hi;
+    ctx->an_gr_scale_lo = ctx->an_gr_any_scale ? scale_lo : 0u;
+    ctx->an_gr_scale_hi = scale_hi;
+    ctx->an_have_graph_targets = true;
+    return MI_OK;
+}
+
+int32_t mi_anim_frame_graph(mi_ctx* ctx, uint32_t n_players, const uint32_t* first_state, uint32_t n_states, const mi_anim_node_state* states, uint32_t flags) {
+    ENTER(ctx);
+    if (flags) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_graph: flags 0x%x", flags);
+    if (!ctx->an_have_tracks || !ctx->an_have_graphs || !ctx->an_have_graph_targets)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_frame_graph before mi_anim_upload_tracks, mi_anim_upload_graphs and mi_anim_upload_graph_targets");
+    if (ctx->an_gr_row_end > ctx->n)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_frame_graph: the targets write row %u, the context has %u rows (upload the targets again)", ctx->an_gr_row_end - 1u, ctx->n);
+    if (ctx->an_gr_player_end > n_players)
+        return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_graph: a target names player %u, n_players = %u", ctx->an_gr_player_end - 1u, n_players);
+    if ((n_players && !first_state) || (n_states && !states)) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_graph: NULL");
+    uint32_t rows = 0;  // targets of the players that run this frame
+    for (uint32_t p = 0; p < n_players; ++p) {
+        if (first_state[p] == MI_ANIM_NO_NODE) continue;
+        if (p >= ctx->an_gr_player_graph.size() || ctx->an_gr_player_graph[p] == MI_ANIM_NO_NODE)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_graph: player %u has states and no graph", p);
+        const uint32_t nodes = ctx->an_gr_graphs[ctx->an_gr_player_graph[p]].n_nodes;
+        if ((uint64_t)first_state[p] + nodes > n_states)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_graph: player %u: states [%u,+%u) exceed %u", p, first_state[p], nodes, n_states);
+        rows += ctx->an_gr_player_count[p];
+    }
+    if (rows == 0) return MI_OK;  // every player that has targets is left alone
+    // ---- one word per player and 8 bytes per state, in the pinned staging block: the kernel reads them where they are ----
+    void *st = nullptr, *d_st = nullptr;
+    int32_t rc = stage_alloc(ctx, ((size_t)n_players + 2u * (size_t)n_states) * 4, &st);
+    if (rc) return rc;
+    memcpy(st, first_state, (size_t)n_players * 4);
+    memcpy((uint32_t*)st + n_players, states, (size_t)n_states * 8);
+    HIP_TRY(ctx, hipHostGetDevicePointer(&d_st, st, 0));
+    IndexedWrite w{};
+    if ((rc = indexed_write_begin(ctx, &w))) return rc;
+    if (ctx->an_gr_any_scale) row_summary_touch(ctx, ROWSUM_PART_SCALE, ctx->an_gr_scale_lo, ctx->an_gr_scale_hi - ctx->an_gr_scale_lo + 1u);
+    AnimGraphArgs a{};
+    a.n_targets = ctx->an_gr_n_targets;
+    a.targets = (const uint32_t*)ctx->an_gr_targets.p;
+    a.bindings = (const uint32_t*)ctx->an_gr_bindings.p;
+    a.wg = (const uint32_t*)ctx->an_gr_wg.p;
+    a.prog = (const uint32_t*)ctx->an_gr_prog.p;
+    a.tracks = (const uint32_t*)ctx->an_tracks.p;
+    a.times = (const float*)ctx->an_times.p;
+    a.values = (const float*)ctx->an_values.p;
+    a.first_state = (const uint32_t*)d_st;
+    a.states = (const uint32_t*)d_st + n_players;
+    a.t = ctx->t, a.r = ctx->r, a.s = ctx->s;
+    a.changed = ctx->changed;
+    a.changed_gen = ctx->changed_gen;
+    a.parent_idx = w.parent_idx;
+    a.mark_bytes = w.mark_cur;
+    a.clear_words = w.clear_other;
+    a.n_clear_words = w.n_clear_words;
+    a.anc = w.anc;
+    HIP_TRY(ctx, launch_anim_graph(a, ctx->stream));
     indexed_write_end(ctx, w, rows);
     return MI_OK;
 }

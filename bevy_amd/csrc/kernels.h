@@ -912,4 +912,47 @@ struct AnimBlendArgs {
 };
 hipError_t launch_anim_blend(AnimBlendArgs a, hipStream_t stream);
 
+// One launch per mi_anim_frame_graph: 192 threads own 64 consecutive targets (in the order mi_anim_upload_graph_targets laid them
+// out: by graph, by player, by row, padded so that a workgroup holds one graph); wave 0 runs the graph's program for the
+// translations, wave 1 for the rotations, wave 2 for the scales (kernels_anim.hip).  Layouts (every index checked on the host):
+//   targets    six columns of n_targets words: row (ANIM_GRAPH_NO_NODE: padding), player, bind0, bind_stride (as AnimBlendArgs),
+//              groups_lo, groups_hi
+//   bindings   as AnimBlendArgs
+//   wg         four words per workgroup: first and count of the key times it stages (as AnimArgs), first instruction and
+//              instruction count of its graph's program
+//   prog       four words per instruction: op | depth << 2 | kind of the node folded into << 6 | node << 8 | skip << 16; the clip
+//              slot (ANIM_OP_CLIP); the node's effective mask, low and high word.  Pre-order, children by ascending node index:
+//              ANIM_OP_ENTER opens an inner node (skip = instructions from it to behind its ANIM_OP_LEAVE), ANIM_OP_CLIP samples a
+//              clip node and folds it into the open node, ANIM_OP_LEAVE folds the open node into the one around it.  Inner nodes
+//              without children emit nothing (they are absent whatever the frame says), so an open node has depth <= 7.
+//   first_state  one word per player, in the pinned staging block: its first state, or ANIM_GRAPH_NO_NODE (left alone)
+//   states     two words per state behind them: weight, seek time
+constexpr uint32_t ANIM_GRAPH_TARGETS = 64u, ANIM_GRAPH_WAVES = 3u;
+constexpr uint32_t ANIM_GRAPH_LEVELS = 7u;  // saved accumulators per lane: the result level and the open nodes of depth 1 .. 6 around the innermost one
+constexpr uint32_t ANIM_GRAPH_MAX_DEPTH = 8u, ANIM_GRAPH_MAX_NODES = 64u, ANIM_GRAPH_NO_NODE = 0xFFFFFFFFu;  // MI_ANIM_* (public header)
+constexpr uint32_t ANIM_NODE_CLIP = 0u, ANIM_NODE_BLEND = 1u, ANIM_NODE_ADD = 2u;
+constexpr uint32_t ANIM_OP_ENTER = 0u, ANIM_OP_CLIP = 1u, ANIM_OP_LEAVE = 2u;
+struct AnimGraphArgs {
+    uint32_t n_targets;          // padding included: a multiple of ANIM_GRAPH_TARGETS
+    uint32_t n_target_wgs;       // as AnimArgs
+    const uint32_t* targets;
+    const uint32_t* bindings;
+    const uint32_t* wg;
+    const uint32_t* prog;
+    const uint32_t* tracks;
+    const float* times;
+    const float* values;
+    const uint32_t* first_state;  // [n_players], pinned host memory mapped into the device
+    const uint32_t* states;       // [n_states] x 2, the same block
+    float *t, *r, *s;
+    uint8_t* changed;
+    uint32_t changed_gen;
+    const uint32_t* parent_idx;  // as AnimArgs
+    uint8_t* mark_bytes;
+    uint32_t* clear_words;
+    uint32_t n_clear_words;
+    const uint32_t* anc;
+};
+hipError_t launch_anim_graph(AnimGraphArgs a, hipStream_t stream);
+
 }  // namespace mi

@@ -18,7 +18,8 @@
 //             when the launch is also the frame's mark_dirty_trees (as k_upload_trs_indexed, kernels_flat.hip), marks the row and
 //             its ancestors; the launch zeroes the other half of the marks when asked to.
 // Arithmetic: glam_math.h (every operation rounded on its own; -ffp-contract=off); acosf / sinf are the device library's.
-// Behind k_anim_frame: k_anim_blend, the same sampling for players that blend several weighted clips (mi_anim_frame_blended).
+// Behind k_anim_frame: k_anim_blend, the same sampling for players that blend several weighted clips (mi_anim_frame_blended), and
+// k_anim_graph, for players that run a whole tree of clip, blend and additive nodes with masks (mi_anim_frame_graph).
 #include "glam_math.h"
 #include "kernels.h"
 
@@ -327,7 +328,180 @@ __global__ __launch_bounds__(ANIM_BLEND_TARGETS* ANIM_BLEND_WAVES) void k_anim_b
         anim_blend_targets<false>(b, AnimTimes<false>{b.times, lds_times, 0u}, tile);
     }
 }
+// ---- animation graphs (mi_anim_frame_graph; kernels.h, AnimGraphArgs) -----------------------------------------------------------
+// 192 threads own 64 consecutive targets of ONE graph (the upload pads at graph seams); lane j of every wave is target j.  The split
+// is by component, not by layer: wave 0 runs the graph's whole program for the translations, wave 1 for the rotations, wave 2 for
+// the scales.  They never exchange data, so behind the staging of the key times there is no barrier; wave 2 (scales: the component
+// a rig most often has no track for) stamps and marks the rows first.  A fourth wave would have nothing to do but that, so 192.
+//   program   the host compiled the tree into ENTER / CLIP / LEAVE instructions (kernels.h).  The program counter, the depth and
+//             every LDS address are the same in all lanes: instructions are read at a wave-uniform address and moved to SGPRs.
+//   alive     which lanes a node counts for is a bit per depth in one VGPR: the parent's bit, the node's weight > 0 in the lane's
+//             player, and the node's effective mask against the lane's groups.  ENTER with no lane alive jumps by its skip
+//             offset; CLIP with no lane alive samples nothing.  Otherwise every lane calls anim_sample, the dead ones with
+//             live = false: the interval search is the wave's.
+//   stack     the accumulator of the innermost open node -- value, weight sum -- lives in registers, and whether a level has a
+//             value yet is a bit per depth beside `alive`.  ENTER saves the registers (and the entered node's weight) into the
+//             wave's LDS stack [level][column][64], LEAVE takes them back and folds the closed node into them: no register array
+//             is indexed by the depth.  W + 2 columns a level, 7 levels: 8 960 B for translations and scales, 10 752 B for
+//             rotations, 28 672 B a workgroup beside the 8 KB of key times -- 36 KB, four workgroups a CU, three waves a SIMD.
+
+template <int W, bool ROT>
+__device__ __forceinline__ void anim_graph_fold(uint32_t kind, AnimVal<W>& acc, float& wsum, bool& any, const AnimVal<W>& v, float weight, bool has) {
+    if (!has) return;
+    if (!any) {  // the first present child, of a BLEND or an ADD node: as it is
+        acc = v, wsum = weight, any = true;
+        return;
+    }
+    if (kind == ANIM_NODE_ADD) {
+        if constexpr (ROT) {
+            const V4 a = anim_slerp(V4{0.0f, 0.0f, 0.0f, 1.0f}, V4{v.v[0], v.v[1], v.v[2], v.v[3]}, weight);
+            const V4 b = V4{acc.v[0], acc.v[1], acc.v[2], acc.v[3]};
+            acc.v[0] = ((a.w * b.x + a.x * b.w) + a.y * b.z) - a.z * b.y;
+            acc.v[1] = ((a.w * b.y - a.x * b.z) + a.y * b.w) + a.z * b.x;
+            acc.v[2] = ((a.w * b.z + a.x * b.y) - a.y * b.x) + a.z * b.w;
+            acc.v[3] = ((a.w * b.w - a.x * b.x) - a.y * b.y) - a.z * b.z;
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e) acc.v[e] = acc.v[e] + v.v[e] * weight;
+        }
+        return;
+    }
+    wsum = wsum + weight;  // (as anim_fold)
+    const float u = f_div(weight, wsum);
+    if constexpr (ROT) {
+        const V4 q = anim_slerp(V4{acc.v[0], acc.v[1], acc.v[2], acc.v[3]}, V4{v.v[0], v.v[1], v.v[2], v.v[3]}, u);
+        acc.v[0] = q.x, acc.v[1] = q.y, acc.v[2] = q.z, acc.v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < W; ++e) acc.v[e] = acc.v[e] + (v.v[e] - acc.v[e]) * u;
+    }
+}
+
+// One wave: the program of its workgroup's graph for component COMP of its 64 targets.  stack: this wave's part of the LDS.
+template <int W, bool ROT, uint32_t COMP, bool STAGED>
+__device__ void anim_graph_eval(const AnimGraphArgs& g, const AnimTimes<STAGED>& ts, float* stack) {
+    constexpr uint32_t LEVEL = (W + 2u) * 64u;
+    const uint32_t lane = threadIdx.x & 63u, gid = blockIdx.x * ANIM_GRAPH_TARGETS + lane;  // (gid < n_targets: padded to whole workgroups)
+    const size_t n = g.n_targets;
+    const uint32_t* tg = g.targets + gid;
+    const uint32_t row = tg[0];
+    uint32_t first = ANIM_GRAPH_NO_NODE, bind0 = 0, stride = 0;
+    uint64_t groups = 0;
+    if (row != ANIM_GRAPH_NO_NODE) {
+        first = g.first_state[tg[n]];
+        bind0 = tg[2u * n], stride = tg[3u * n];
+        groups = (uint64_t)tg[4u * n] | (uint64_t)tg[5u * n] << 32;
+    }
+    const bool active = first != ANIM_GRAPH_NO_NODE;
+    if (COMP == 2u && active) {
+        g.changed[row] = (uint8_t)g.changed_gen;
+        if (g.mark_bytes) mark_row_and_ancestors(row, g.parent_idx, g.mark_bytes, g.anc, 0xFFFFu);
+    }
+    if (__ballot(active) == 0) return;
+    const uint32_t* wg = g.wg + 4u * blockIdx.x;
+    const uint32_t prog0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wg[2]), prog_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)wg[3]);
+    AnimArgs a{};  // what anim_sample reads of it: the two pools
+    a.tracks = g.tracks, a.values = g.values;
+    AnimVal<W> acc{};
+    float wsum = 0.0f;
+    uint32_t alive = active ? 1u : 0u, present = 0u;  // bit d: the open node of depth d counts for this lane / has a value (bit 0: the result)
+    for (uint32_t pc = 0; pc < prog_n;) {
+        const uint4 in = reinterpret_cast<const uint4*>(g.prog)[prog0 + pc];
+        const uint32_t head = (uint32_t)__builtin_amdgcn_readfirstlane((int)in.x);
+        const uint32_t op = head & 3u, d = (head >> 2) & 15u, into = (head >> 6) & 3u, node = (head >> 8) & 0xFFu;
+        if (op == ANIM_OP_LEAVE) {  // the open node of depth d is complete: fold it into the one saved at level d - 1
+            const float* c = stack + (d - 1u) * LEVEL + lane;
+            AnimVal<W> outer;
+#pragma unroll
+            for (int e = 0; e < W; ++e) outer.v[e] = c[e * 64];
+            float outer_wsum = c[W * 64];
+            bool outer_any = (present >> (d - 1u)) & 1u;
+            anim_graph_fold<W, ROT>(into, outer, outer_wsum, outer_any, acc, c[(W + 1) * 64], (present >> d) & 1u);
+            acc = outer, wsum = outer_wsum;
+            present = (present & ~(3u << (d - 1u))) | ((outer_any ? 1u : 0u) << (d - 1u));
+            ++pc;
+            continue;
+        }
+        float weight = 0.0f, x = 0.0f;
+        if (active) {
+            const uint32_t* st = g.states + 2ull * ((uint64_t)first + node);
+            weight = __uint_as_float(st[0]), x = __uint_as_float(st[1]);
+        }
+        const uint64_t mask = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)in.z) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)in.w) << 32;
+        const bool on = ((alive >> (d - 1u)) & 1u) && weight > 0.0f && (mask & groups) == 0;  // (a NaN weight: not on)
+        if (op == ANIM_OP_ENTER) {
+            if (__ballot(on) == 0) {  // the subtree is dead in every lane
+                pc += head >> 16;
+                continue;
+            }
+            float* c = stack + (d - 1u) * LEVEL + lane;
+#pragma unroll
+            for (int e = 0; e < W; ++e) c[e * 64] = acc.v[e];
+            c[W * 64] = wsum, c[(W + 1) * 64] = weight;
+            alive = (alive & ~(1u << d)) | ((on ? 1u : 0u) << d);
+            present &= ~(1u << d);
+            ++pc;
+            continue;
+        }
+        if (__ballot(on) != 0) {  // ANIM_OP_CLIP
+            const uint32_t clip = (uint32_t)__builtin_amdgcn_readfirstlane((int)in.y);
+            uint32_t track = ANIM_NO_TRACK;
+            if (on) track = g.bindings[(size_t)bind0 + (size_t)(3u * clip + COMP) * stride];
+            AnimVal<W> v{};
+            const bool has = anim_sample<W, ROT>(a, ts, track, on, x, lane, v);
+            bool any = (present >> (d - 1u)) & 1u;
+            anim_graph_fold<W, ROT>(into, acc, wsum, any, v, weight, has);
+            present |= (any ? 1u : 0u) << (d - 1u);
+        }
+        ++pc;
+    }
+    if (!(present & 1u)) return;  // the root is absent for this component: not written
+    if constexpr (ROT) {
+        reinterpret_cast<float4*>(g.r)[row] = make_float4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+    } else {
+        float* o = (COMP == 0u ? g.t : g.s) + 3ull * row;
+        o[0] = acc.v[0], o[1] = acc.v[1], o[2] = acc.v[2];
+    }
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void anim_graph_targets(const AnimGraphArgs& g, const AnimTimes<STAGED>& ts, float* stack) {
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave == 0u) anim_graph_eval<3, false, 0u>(g, ts, stack);
+    else if (wave == 1u) anim_graph_eval<4, true, 1u>(g, ts, stack + ANIM_GRAPH_LEVELS * 5u * 64u);
+    else anim_graph_eval<3, false, 2u>(g, ts, stack + ANIM_GRAPH_LEVELS * 11u * 64u);
+}
+
+__global__ __launch_bounds__(ANIM_GRAPH_TARGETS* ANIM_GRAPH_WAVES) void k_anim_graph(AnimGraphArgs g) {
+    constexpr uint32_t THREADS = ANIM_GRAPH_TARGETS * ANIM_GRAPH_WAVES;
+    __shared__ float lds_times[ANIM_LDS_TIMES];
+    __shared__ float stack[ANIM_GRAPH_LEVELS * 16u * 64u];  // (5 + 6 + 5 columns a level: t, r, s)
+    if (g.clear_words)
+        for (uint32_t w = blockIdx.x * THREADS + threadIdx.x; w < g.n_clear_words; w += gridDim.x * THREADS) g.clear_words[w] = 0u;
+    if (blockIdx.x >= g.n_target_wgs) return;  // (whole workgroups)
+    const uint32_t lo = g.wg[4u * blockIdx.x], n = g.wg[4u * blockIdx.x + 1u];  // (n <= ANIM_LDS_TIMES: the upload saw to it)
+    if (n) {  // (workgroup-uniform)
+        for (uint32_t j = threadIdx.x; j < n; j += THREADS) lds_times[j] = g.times[lo + j];
+        __syncthreads();
+        anim_graph_targets<true>(g, AnimTimes<true>{g.times, lds_times, lo}, stack);
+    } else {
+        anim_graph_targets<false>(g, AnimTimes<false>{g.times, lds_times, 0u}, stack);
+    }
+}
 }  // namespace
+
+hipError_t launch_anim_graph(AnimGraphArgs a, hipStream_t stream) {
+    if (a.n_targets == 0) return hipSuccess;
+    a.n_target_wgs = a.n_targets / ANIM_GRAPH_TARGETS;
+    uint32_t grid = a.n_target_wgs;
+    if (a.clear_words) {  // (as launch_anim_frame)
+        const uint32_t cb = (a.n_clear_words + 1023u) / 1024u < 1024u ? (a.n_clear_words + 1023u) / 1024u : 1024u;
+        grid = grid > cb ? grid : cb;
+    }
+    if (!a.mark_bytes) a.anc = nullptr;
+    MI_LAUNCH(k_anim_graph, dim3(grid), dim3(ANIM_GRAPH_TARGETS * ANIM_GRAPH_WAVES), 0, stream, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_anim_blend(AnimBlendArgs a, hipStream_t stream) {
     if (a.n_targets == 0) return hipSuccess;

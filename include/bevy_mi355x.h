@@ -878,9 +878,9 @@ int32_t mi_skin_download_bounds(mi_ctx* ctx, uint32_t first_skin, uint32_t n, fl
  * animation target of a player that plays ONE clip at weight 1, computed on the device from a resident pool of keyframe tracks and
  * one float per player -- its seek time -- instead of being sampled on a core and uploaded, 40 bytes per joint and frame.
  * Players that blend one level of weighted clips -- a transition's crossfade, a flat blend node over clip nodes -- go through
- * mi_anim_upload_blend_targets / mi_anim_frame_blended below.  Out of scope: nested blend nodes, additive nodes and masks, morph
- * weights, and advancing the players' clocks.  The host advances the seek times and the weights, and keeps the stock system for
- * players whose graph is more than one level of weighted clips.
+ * mi_anim_upload_blend_targets / mi_anim_frame_blended below; players whose graph is more than that -- nested blend nodes,
+ * additive nodes, masks -- through mi_anim_upload_graphs / mi_anim_upload_graph_targets / mi_anim_frame_graph behind them.  Out of
+ * scope: morph weights, and advancing the players' clocks.  The host advances the seek times and the weights.
  * The reference sources were not at hand when this was written: the arithmetic stated here is the library's definition, in glam's
  * operation order as everywhere else, and has NOT been pinned against a run of the reference.
  *
@@ -993,6 +993,81 @@ typedef struct mi_anim_layer {
 int32_t mi_anim_upload_blend_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_blend_target* targets, uint32_t n_bindings,
                                      const mi_anim_binding* bindings);
 int32_t mi_anim_frame_blended(mi_ctx* ctx, uint32_t n_players, uint32_t n_layers, const mi_anim_layer* layers, uint32_t flags);
+
+/* Animation graphs: a whole AnimationGraph per player -- a tree of CLIP, BLEND and ADD nodes with per-node weights and masks --
+ * evaluated for every target in one launch, over the same track pool and the same sampling.  A third state beside the two above.
+ *
+ *   mi_anim_upload_graphs  replaces all graphs and drops the graph targets.  Graph g is nodes[first_node, first_node + n_nodes);
+ *                    `parent` is an index within the graph.  Node 0 is the root (parent MI_ANIM_NO_NODE) and the only one; every
+ *                    other node's parent is below its own index.  The children of a node are taken in ascending node index: the
+ *                    host renumbers so that the sibling order survives.  `clip` is a clip slot of the targets' bindings, read for
+ *                    CLIP nodes only.  mask_lo / mask_hi is the node's own 64-bit mask; the effective mask of a node is its own
+ *                    | its parent's effective mask.  A root that is a CLIP node is allowed.  MI_ERR_INVALID_ARG with a message,
+ *                    the previous state left in place: an unknown kind; a CLIP node that is a parent; a node range outside the
+ *                    array; n_nodes == 0 or > MI_ANIM_MAX_GRAPH_NODES; a depth above MI_ANIM_MAX_GRAPH_DEPTH (the root is 1); a
+ *                    parent not below the node; a second root.
+ *   mi_anim_upload_graph_targets  replaces the graph targets (mi_anim_upload_tracks and mi_anim_upload_graphs drop them).  Targets
+ *                    and bindings as mi_anim_upload_blend_targets; groups_lo / groups_hi is the target's 64 mask groups;
+ *                    player_graph[player] is the graph a player runs, or MI_ANIM_NO_NODE for a player without one, who may have
+ *                    no targets.  Checked as the blend targets are, and: player < n_players; the player's graph exists; every
+ *                    CLIP node's clip is below the smallest n_clips of the player's targets.  MI_ERR_NOT_READY before the tracks
+ *                    and the graphs.  The library orders the targets by graph, by player, by row, and pads so that no block
+ *                    of 64 targets holds two graphs.
+ *   mi_anim_frame_graph  one kernel launch, asynchronous; call it before mi_propagate.  first_state[p] == MI_ANIM_NO_NODE: player
+ *                    p is left alone, its rows neither written nor stamped.  Otherwise states[first_state[p] + k] is node k's
+ *                    effective weight this frame (the host multiplies the node's weight by the active animation's) and, for a
+ *                    CLIP node, its seek time; the range must lie inside `states` and the player must have a graph
+ *                    (MI_ERR_INVALID_ARG).  MI_ERR_NOT_READY and a target's player >= n_players as mi_anim_frame; flags: pass 0.
+ *                    For the rows of the players that run, the call is the twin of mi_upload_transforms_indexed, as its siblings
+ *                    are.  One word per player and 8 bytes per state travel in the pinned staging block; no copy in front.
+ * The evaluation, per component (translation, rotation, scale) separately, every operation rounded on its own (no fused
+ * multiply-add).  eval(node) is a value or ABSENT:
+ *     any node    ABSENT when its weight is not > 0 (zero, negative, NaN) or (effective mask & the target's groups) != 0: either
+ *                 removes the whole subtree
+ *     CLIP        ABSENT when the binding has MI_ANIM_NO_TRACK for the component; else the track sampled at the node's seek time
+ *     BLEND       the present children folded in order exactly as mi_anim_frame_blended folds layers, weight = the child's:
+ *                 first acc = v, W = w; a later one W = W + w, u = w / W, acc = acc + (v - acc) * u, rotation acc = slerp(acc, v, u)
+ *     ADD         first present child acc = v, whatever its weight; a later one acc = acc + v * w per component, rotation
+ *                 acc = mul(slerp(IDENTITY, v, w), acc) -- the slerp above, sign flip and 0.9995 branch included, and mul(a, b):
+ *                   x = ((a.w b.x + a.x b.w) + a.y b.z) - a.z b.y      y = ((a.w b.y - a.x b.z) + a.y b.w) + a.z b.x
+ *                   z = ((a.w b.z + a.x b.y) - a.y b.x) + a.z b.w      w = ((a.w b.w - a.x b.x) - a.y b.y) - a.z b.z
+ *     an inner node with no present child is ABSENT
+ * The root's value is written; a component whose root is ABSENT is not written, the row's change byte is stamped all the same.
+ * So a root BLEND whose children are all CLIP nodes gives, bit for bit, what mi_anim_frame_blended writes for the same layers, and
+ * a root CLIP, or a root with one present clip, what mi_anim_frame writes.  The library's definition: not pinned against a run of
+ * the reference.
+ * Cost (profiles/r12_graph/ab.md, one run, wall clock): mi_anim_frame_graph + mi_propagate for 1 000 rigs x 24 joints running
+ * add(blend(blend(c0,c1),c2),c3) 65 us, 40 000 rigs 519 us; numpy evaluation on a core + mi_upload_transforms_indexed +
+ * mi_propagate 7.0 ms and 280 ms.  A flat two-clip graph through this call against mi_anim_frame_blended on the same work:
+ * 40 us against 42 us at 1 000 rigs, 314 us against 425 us at 40 000 -- flat graphs may go through either call; players that play
+ * one clip stay on mi_anim_frame.  Not measured: the kernels on their own (both numbers hold the host's share of the call),
+ * masks, deep graphs and many graphs in one launch at scale, scattered rows, tracks too long for LDS. */
+#define MI_ANIM_NODE_CLIP 0u
+#define MI_ANIM_NODE_BLEND 1u
+#define MI_ANIM_NODE_ADD 2u
+#define MI_ANIM_NO_NODE 0xFFFFFFFFu
+#define MI_ANIM_MAX_GRAPH_DEPTH 8u /* root = depth 1 */
+#define MI_ANIM_MAX_GRAPH_NODES 64u /* per graph */
+typedef struct mi_anim_graph_node {
+    uint32_t kind, parent, clip;  /* MI_ANIM_NODE_*; index within the graph, or MI_ANIM_NO_NODE; clip slot (CLIP nodes) */
+    uint32_t mask_lo, mask_hi;    /* the node's own mask */
+} mi_anim_graph_node;
+typedef struct mi_anim_graph {
+    uint32_t first_node, n_nodes;
+} mi_anim_graph;
+typedef struct mi_anim_graph_target {
+    uint32_t row, player;
+    uint32_t first_binding, n_clips;  /* as mi_anim_blend_target */
+    uint32_t groups_lo, groups_hi;    /* the target's mask groups */
+} mi_anim_graph_target;
+typedef struct mi_anim_node_state {
+    float weight, seek_time;
+} mi_anim_node_state;
+int32_t mi_anim_upload_graphs(mi_ctx* ctx, uint32_t n_graphs, const mi_anim_graph* graphs, uint32_t n_nodes, const mi_anim_graph_node* nodes);
+int32_t mi_anim_upload_graph_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_graph_target* targets, uint32_t n_bindings,
+                                     const mi_anim_binding* bindings, uint32_t n_players, const uint32_t* player_graph);
+int32_t mi_anim_frame_graph(mi_ctx* ctx, uint32_t n_players, const uint32_t* first_state, uint32_t n_states, const mi_anim_node_state* states,
+                            uint32_t flags);
 
 /* ======================================================================================= */
 /* camera helpers (pure host code; what update_frusta computes, visibility/mod.rs:627-636)   */

@@ -25,7 +25,9 @@ STRUCT_RUST = {"mi_ctx": "MiCtx", "mi_view": "MiView", "mi_cluster_view": "MiClu
                "mi_batch_totals": "MiBatchTotals", "mi_sorted_item": "MiSortedItem", "mi_sorted_batch": "MiSortedBatch", "mi_unbatchable_index": "MiUnbatchableIndex",
                "mi_frame_results": "MiFrameResults", "mi_visible_list": "MiVisibleList", "mi_upload_window": "MiUploadWindow",
                "mi_hierarchy_advice": "MiHierarchyAdvice", "mi_skin": "MiSkin", "mi_joint_aabb": "MiJointAabb", "mi_anim_track": "MiAnimTrack", "mi_anim_target": "MiAnimTarget",
-               "mi_anim_binding": "MiAnimBinding", "mi_anim_blend_target": "MiAnimBlendTarget", "mi_anim_layer": "MiAnimLayer"}
+               "mi_anim_binding": "MiAnimBinding", "mi_anim_blend_target": "MiAnimBlendTarget", "mi_anim_layer": "MiAnimLayer",
+               "mi_anim_graph_node": "MiAnimGraphNode", "mi_anim_graph": "MiAnimGraph", "mi_anim_graph_target": "MiAnimGraphTarget",
+               "mi_anim_node_state": "MiAnimNodeState"}
 
 
 def strip_comments(src):

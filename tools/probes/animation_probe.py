@@ -4,7 +4,10 @@ test's reference from its float64 run on the test's own inputs (no GPU needed fo
     python tools/probes/animation_probe.py [--deviation] [--rigs 1000,40000] [--reps 30]
 profiles/r11_blend/ab.md: --blend, the crossfade scene -- every rig's player with two layers of a shared pair of clips at weights 0.3 /
 0.7 through mi_anim_frame_blended, the same with one layer beside mi_anim_frame on identical work, and the host path (numpy sampling
-and blending + mi_upload_transforms_indexed); --blend-deviation, the float32 run of test_gpu_anim_blend's reference (no GPU needed)."""
+and blending + mi_upload_transforms_indexed); --blend-deviation, the float32 run of test_gpu_anim_blend's reference (no GPU needed).
+profiles/r12_graph/ab.md: --graph, (a) a nested graph with an additive clip through mi_anim_frame_graph against its numpy evaluation +
+mi_upload_transforms_indexed, (b) a flat two-clip graph through mi_anim_frame_graph against mi_anim_frame_blended on the same work;
+--graph-deviation, the float32 run of test_gpu_anim_graph's reference per shape (no GPU needed)."""
 import argparse
 import os
 import sys
@@ -212,6 +215,110 @@ def blend_ab(rigs, reps):
     print(f"  numpy sampling and blending + upload_transforms_indexed + propagate {quartiles(took['host'])}  (sampling and blending alone {quartiles(took['host sampling'])})")
 
 
+def graph_deviation():
+    import test_gpu_anim_graph as T
+    cases = [(f"{name}, {lay}", T.nested_scene(name, lay)) for name, lay in T.NESTED] + [(what, T.mask_scene(what)) for what in T.MASKS]
+    rot, lerp = {name: 0.0 for name in T.SHAPES}, 0.0
+    for what, sc in cases:
+        sc["rot_bound"] = [-1.0 - g for g in range(len(sc["names"]))]  # (a marker per graph in place of the bound)
+        (w64, bound), (w32, _) = [T.expected(sc, dt) for dt in (np.float64, F32)]  # (both runs assert the slerps' preconditions)
+        for c in range(3):
+            exact, err = bound[c] == 0, np.abs(w32[c] - w64[c])
+            assert np.array_equal(w32[c][exact], w64[c][exact]), (what, c)
+            for g, name in enumerate(sc["names"]):
+                rot[name] = max(rot[name], np.max(err[bound[c] == -1.0 - g], initial=0.0) / T.E)
+            rest = bound[c] > 0
+            lerp = max(lerp, np.max(err[rest] / bound[c][rest], initial=0.0))
+    print(f"float32 numpy against float64 over the {len(cases)} nested and mask cases (T.SEEDS): translation / scale and single clips worst error / bound {lerp:.2f}")
+    for name, dev in rot.items():
+        print(f"  folded rotations of {name}: worst {dev:.2f} x 2^-24 (the test's ROT_DEVIATION: {T.ROT_DEVIATION[name]})")
+
+
+DEEP = [(2, 0xFFFFFFFF, 0), (1, 0, 0), (1, 1, 0), (0, 2, 0), (0, 2, 1), (0, 1, 2), (0, 0, 3)]  # add(blend(blend(c0,c1),c2),c3): kind, parent, clip
+FLAT = [(1, 0xFFFFFFFF, 0), (0, 0, 0), (0, 0, 1)]                                               # blend(c0,c1)
+
+
+def graph_ab(rigs, reps):
+    """Four clips over the same 24 joints, bindings shared by every rig.  (a) DEEP through anim_frame_graph against its numpy evaluation
+    (lerp + normalize for every rotation step, the cheaper arithmetic) + upload_transforms_indexed; (b) FLAT against anim_frame_blended."""
+    rng = np.random.default_rng(rigs)
+    clips = [clip(rng) for _ in range(4)]
+    tracks = np.concatenate([c[0] for c in clips])
+    for c in range(1, 4):
+        tracks["first_time"][3 * JOINTS * c:3 * JOINTS * (c + 1)] += KEYS * c
+        tracks["first_value"][3 * JOINTS * c:3 * JOINTS * (c + 1)] += c * len(clips[0][2])
+    times, values = np.concatenate([c[1] for c in clips]), np.concatenate([c[2] for c in clips])
+    n = rigs * JOINTS
+    bindings = np.zeros(4 * JOINTS, B.ANIM_BINDING_DTYPE)
+    for k, f in enumerate(("track_t", "track_r", "track_s")):
+        bindings[f] = 3 * JOINTS * (np.arange(4 * JOINTS) % 4) + 3 * (np.arange(4 * JOINTS) // 4) + k
+    targets, blend_targets = np.zeros(n, B.ANIM_GRAPH_TARGET_DTYPE), np.zeros(n, B.ANIM_BLEND_TARGET_DTYPE)
+    for tg in (targets, blend_targets):
+        tg["row"], tg["player"], tg["first_binding"], tg["n_clips"] = np.arange(n), np.arange(n) // JOINTS, 4 * (np.arange(n) % JOINTS), 4
+    vals = [[np.stack([c[2][c[0][3 * j + k]["first_value"]:][:KEYS * w].reshape(KEYS, w) for j in range(JOINTS)]) for k, w in enumerate((3, 4, 3))] for c in clips]
+    nodes = np.array([(*nd, 0, 0) for nd in DEEP + FLAT], B.ANIM_GRAPH_NODE_DTYPE)
+    graphs = np.array([(0, len(DEEP)), (len(DEEP), len(FLAT))], B.ANIM_GRAPH_DTYPE)
+    w_deep, w_flat = np.array([1, 0.8, 0.6, 0.3, 0.7, 0.5, 0.25], F32), np.array([1, 0.3, 0.7], F32)
+    deep, flat, layers = np.zeros(7 * rigs, B.ANIM_NODE_STATE_DTYPE), np.zeros(3 * rigs, B.ANIM_NODE_STATE_DTYPE), np.zeros(2 * rigs, B.ANIM_LAYER_DTYPE)
+    deep["weight"], flat["weight"] = np.tile(w_deep, rigs), np.tile(w_flat, rigs)
+    layers["player"], layers["clip"], layers["weight"] = np.arange(2 * rigs) // 2, np.arange(2 * rigs) % 2, np.tile(w_flat[1:], rigs)
+    rows = np.arange(n, dtype=U32)
+    took = {k: [] for k in ("deep", "host", "host evaluation", "flat", "blended")}
+    with B.Context() as ctx:
+        ctx.resize(n)
+        ctx.upload_transforms(np.zeros(3 * n, F32), np.tile(np.array([0, 0, 0, 1], F32), n), np.ones(3 * n, F32))
+        ctx.propagate()
+        ctx.anim_upload_tracks(tracks, times, values)
+        ctx.anim_upload_blend_targets(blend_targets, bindings)
+        ctx.anim_upload_graphs(graphs, nodes)
+
+        def timed(key, fn, keep):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ctx.propagate(0)
+            ctx.synchronize()
+            if keep:
+                took[key].append(time.perf_counter() - t0)
+
+        def host_path(x, keep):
+            t0 = time.perf_counter()
+            v = [host_sample(clips[c][1], vals[c], x[:, c]) for c in range(4)]
+            unit = lambda q: q / np.linalg.norm(q, axis=1, keepdims=True)
+            out = []
+            for k in range(3):
+                inner = v[0][k] + (v[1][k] - v[0][k]) * F32(0.7)  # u = 0.7 / (0.3 + 0.7)
+                outer = inner + (v[2][k] - inner) * F32(0.5 / 1.1)
+                if k != 1:
+                    out.append(outer + v[3][k] * F32(0.25))
+                    continue
+                a, b = unit(np.array([0, 0, 0, 1], F32) + (v[3][k] - np.array([0, 0, 0, 1], F32)) * F32(0.25)).T, unit(unit(inner) + (v[2][k] - unit(inner)) * F32(0.5 / 1.1)).T
+                out.append(np.stack([a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0],
+                                     a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3], a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]], axis=1))
+            if keep:
+                took["host evaluation"].append(time.perf_counter() - t0)
+            ctx.upload_transforms_indexed(rows, *[np.ascontiguousarray(o, F32).reshape(-1) for o in out])
+
+        for which, first, run in ((0, 7 * np.arange(rigs), ("deep", "host")), (1, 3 * np.arange(rigs), ("flat", "blended"))):
+            ctx.anim_upload_graph_targets(targets, bindings, np.full(rigs, which, U32))
+            for rep in range(reps + 5):  # (five warm-up frames; the two paths alternate)
+                x = rng.uniform(0.01, 0.99, (rigs, 4)).astype(F32)
+                deep["seek_time"].reshape(rigs, 7)[:, [3, 4, 5, 6]] = x
+                flat["seek_time"].reshape(rigs, 3)[:, 1:] = x[:, :2]
+                layers["seek_time"] = x[:, :2].reshape(-1)
+                if which == 0:
+                    timed("deep", lambda: ctx.anim_frame_graph(first, deep), rep >= 5)
+                    timed("host", lambda: host_path(x, rep >= 5), rep >= 5)
+                else:
+                    timed("flat", lambda: ctx.anim_frame_graph(first, flat), rep >= 5)
+                    timed("blended", lambda: ctx.anim_frame_blended(rigs, layers), rep >= 5)
+    print(f"{rigs} rigs x {JOINTS} joints, {reps} frames, wall clock around synchronize:")
+    print(f"  (a) anim_frame_graph, add(blend(blend(c0,c1),c2),c3) + propagate        {quartiles(took['deep'])}")
+    print(f"      numpy evaluation + upload_transforms_indexed + propagate             {quartiles(took['host'])}  (the evaluation alone {quartiles(took['host evaluation'])})")
+    print(f"  (b) anim_frame_graph, blend(c0,c1) at 0.3 / 0.7 + propagate              {quartiles(took['flat'])}")
+    print(f"      anim_frame_blended, the same two layers + propagate                  {quartiles(took['blended'])}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--deviation", action="store_true")
@@ -219,9 +326,16 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--blend", action="store_true")
     ap.add_argument("--blend-deviation", action="store_true")
+    ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--graph-deviation", action="store_true")
     a = ap.parse_args()
     if a.deviation:
         deviation()
+    elif a.graph_deviation:
+        graph_deviation()
+    elif a.graph:
+        for rigs in a.rigs.split(","):
+            graph_ab(int(rigs), a.reps)
     elif a.blend_deviation:
         blend_deviation()
     elif a.blend:
