@@ -17,6 +17,7 @@ from .api import (  # noqa: F401
     ANIM_MAX_GRAPH_DEPTH,
     ANIM_MAX_GRAPH_NODES,
     ANIM_MAX_LAYERS,
+    ANIM_MORPH_TARGET_DTYPE,
     ANIM_NODE_ADD,
     ANIM_NODE_BLEND,
     ANIM_NODE_CLIP,
@@ -29,6 +30,8 @@ from .api import (  # noqa: F401
     ANIM_TARGET_DTYPE,
     ANIM_TRACK_DTYPE,
     ANIM_TRANSLATION,
+    ANIM_WEIGHT_TRACK_DTYPE,
+    BUF_MORPH_WEIGHTS,
     ClusterView,
     Context,
     MiError,

@@ -206,6 +206,11 @@ ANIM_GRAPH_DTYPE = np.dtype([("first_node", np.uint32), ("n_nodes", np.uint32)])
 ANIM_GRAPH_TARGET_DTYPE = np.dtype([("row", np.uint32), ("player", np.uint32), ("first_binding", np.uint32), ("n_clips", np.uint32), ("groups_lo", np.uint32),
                                     ("groups_hi", np.uint32)])  # mi_anim_graph_target
 ANIM_NODE_STATE_DTYPE = np.dtype([("weight", np.float32), ("seek_time", np.float32)])  # mi_anim_node_state
+BUF_MORPH_WEIGHTS = 17  # device_buffer(which): the output array of anim_frame_weights
+ANIM_WEIGHT_TRACK_DTYPE = np.dtype([("first_time", np.uint32), ("n_keys", np.uint32), ("first_value", np.uint32), ("interp", np.uint32),
+                                    ("n_weights", np.uint32)])  # mi_anim_weight_track
+ANIM_MORPH_TARGET_DTYPE = np.dtype([("player", np.uint32), ("first_weight", np.uint32), ("n_weights", np.uint32), ("first_binding", np.uint32),
+                                    ("n_clips", np.uint32), ("groups_lo", np.uint32), ("groups_hi", np.uint32)])  # mi_anim_morph_target
 
 ABI_SYMBOLS = [
     "mi_abi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_last_error_string", "mi_synchronize",
@@ -225,6 +230,7 @@ ABI_SYMBOLS = [
     "mi_batch_sorted_build", "mi_upload_depth_bias", "mi_phase_sort", "mi_phase_sort_download", "mi_skin_upload_inverse_bindposes", "mi_skin_upload", "mi_skin_frame", "mi_skin_download_matrices", "mi_skin_download_bounds",
     "mi_anim_upload_tracks", "mi_anim_upload_targets", "mi_anim_frame", "mi_anim_upload_blend_targets", "mi_anim_frame_blended",
     "mi_anim_upload_graphs", "mi_anim_upload_graph_targets", "mi_anim_frame_graph",
+    "mi_anim_upload_weight_tracks", "mi_anim_upload_morph_targets", "mi_anim_frame_weights", "mi_anim_download_weights",
     "mi_batch_download_totals", "mi_batch_download", "mi_perspective_clip_from_view", "mi_compute_frustum",
     "mi_bind_visibility_output", "mi_exchange_set_mode", "mi_exchange_configure", "mi_exchange_configure_multi", "mi_exchange_configure_owned", "mi_exchange_group_flush", "mi_exchange_last", "mi_exchange_download", "mi_device_buffer",
 ]
@@ -940,6 +946,42 @@ class Context:
         st = np.ascontiguousarray(states, ANIM_NODE_STATE_DTYPE).reshape(-1)
         self._ck(self._lib.mi_anim_frame_graph(self._h, len(fs), fs.ctypes.data_as(C.c_void_p) if len(fs) else None, len(st),
                                                st.ctypes.data_as(C.c_void_p) if len(st) else None, C.c_uint32(0)))
+
+    def anim_upload_weight_tracks(self, tracks, times, values):
+        """Replaces the pool of weight tracks (and drops the morph targets).  tracks: ANIM_WEIGHT_TRACK_DTYPE[n]; times f32[...] and
+        values f32[...]: pools of their own, n_weights floats per key (ANIM_CUBIC: n in-tangents, n values, n out-tangents)."""
+        tr = np.ascontiguousarray(tracks, ANIM_WEIGHT_TRACK_DTYPE).reshape(-1)
+        tm, va = _f32(times).reshape(-1), _f32(values).reshape(-1)
+        self._ck(self._lib.mi_anim_upload_weight_tracks(self._h, len(tr), tr.ctypes.data_as(C.c_void_p) if len(tr) else None, len(tm),
+                                                        _ptr(tm, C.c_float) if len(tm) else None, len(va), _ptr(va, C.c_float) if len(va) else None))
+
+    def anim_upload_morph_targets(self, targets, bindings, player_graph, n_weights_out, initial_weights=None):
+        """targets: ANIM_MORPH_TARGET_DTYPE[n] (the player, the range of the output array written, the range of `bindings`, the mask
+        groups); bindings: u32[m], a weight track or ANIM_NO_TRACK per target and clip slot; player_graph: u32 per player;
+        initial_weights: f32[n_weights_out], or None = zeros."""
+        tg = np.ascontiguousarray(targets, ANIM_MORPH_TARGET_DTYPE).reshape(-1)
+        bd, pg, iw = _u32(bindings).reshape(-1), _u32(player_graph).reshape(-1), _f32(initial_weights)
+        if iw is not None and iw.size != n_weights_out:
+            raise ValueError(f"initial_weights holds {iw.size} floats, n_weights_out = {n_weights_out}")
+        self._ck(self._lib.mi_anim_upload_morph_targets(self._h, len(tg), tg.ctypes.data_as(C.c_void_p) if len(tg) else None, len(bd),
+                                                        _ptr(bd, C.c_uint32) if len(bd) else None, len(pg), _ptr(pg, C.c_uint32) if len(pg) else None,
+                                                        C.c_uint32(n_weights_out), _ptr(iw, C.c_float) if iw is not None and iw.size else None))
+        self._n_morph_weights = int(n_weights_out)
+
+    def anim_frame_weights(self, first_state, states):
+        """Every morph target's weights from its player's graph; first_state and states as anim_frame_graph's.  Writes the output
+        array (download_weights, device_buffer(BUF_MORPH_WEIGHTS)) and nothing else."""
+        fs = np.ascontiguousarray(first_state, np.uint32).reshape(-1)
+        st = np.ascontiguousarray(states, ANIM_NODE_STATE_DTYPE).reshape(-1)
+        self._ck(self._lib.mi_anim_frame_weights(self._h, len(fs), fs.ctypes.data_as(C.c_void_p) if len(fs) else None, len(st),
+                                                 st.ctypes.data_as(C.c_void_p) if len(st) else None, C.c_uint32(0)))
+
+    def anim_download_weights(self, first_weight=0, n=None):
+        """-> f32[n]: weights [first_weight, first_weight + n) of the output array (all behind first_weight by default)."""
+        n = getattr(self, "_n_morph_weights", 0) - first_weight if n is None else n
+        out = np.zeros(max(n, 1), np.float32)
+        self._ck(self._lib.mi_anim_download_weights(self._h, int(first_weight), int(n), _ptr(out, C.c_float)))
+        return out[:n]
 
     def batch_download(self):
         """-> dict: work_items / metadata / batch_sets (lists indexed by mesh class, u32 arrays), records u32[k, 8], unbatchable

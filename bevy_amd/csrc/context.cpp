@@ -1030,7 +1030,8 @@ int32_t mi_ctx_destroy(mi_ctx* ctx) {
                       &ctx->cl_offsets, &ctx->cl_indices, &ctx->cl_scalars, &ctx->ps_pairs[0], &ctx->ps_pairs[1], &ctx->ps_table, &ctx->ps_rows,
                       &ctx->ps_keys, &ctx->ps_dist, &ctx->ps_count, &ctx->sk_pool, &ctx->sk_joint_rows, &ctx->sk_slot_bind, &ctx->sk_bounded, &ctx->sk_aabbs,
                       &ctx->sk_bounds, &ctx->sk_mats[0], &ctx->sk_mats[1], &ctx->an_tracks, &ctx->an_times, &ctx->an_values, &ctx->an_targets, &ctx->an_wg_times,
-                      &ctx->an_bl_targets, &ctx->an_bl_bindings, &ctx->an_bl_wg_times, &ctx->an_gr_prog, &ctx->an_gr_targets, &ctx->an_gr_bindings, &ctx->an_gr_wg};
+                      &ctx->an_bl_targets, &ctx->an_bl_bindings, &ctx->an_bl_wg_times, &ctx->an_gr_prog, &ctx->an_gr_targets, &ctx->an_gr_bindings, &ctx->an_gr_wg,
+                      &ctx->an_mw_tracks, &ctx->an_mw_times, &ctx->an_mw_values, &ctx->an_mw_chunks, &ctx->an_mw_bindings, &ctx->an_mw_out};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& sl : ctx->cl_parked)  // (the parked cluster views' buffers; the selected one's are in the list above)
@@ -2619,6 +2620,7 @@ int32_t mi_device_buffer(mi_ctx* ctx, uint32_t which, void** out_ptr, uint64_t* 
     case MI_BUF_TRANSLATION: p = ctx->t; bytes = (uint64_t)ctx->n * 12; break;
     case MI_BUF_ROTATION: p = ctx->r; bytes = (uint64_t)ctx->n * 16; break;
     case MI_BUF_SCALE: p = ctx->s; bytes = (uint64_t)ctx->n * 12; break;
+    case MI_BUF_MORPH_WEIGHTS: p = ctx->an_mw_have_out ? ctx->an_mw_out.p : nullptr; bytes = (uint64_t)ctx->an_mw_n_out * 4; break;
     default: return fail(ctx, MI_ERR_INVALID_ARG, "mi_device_buffer: unknown buffer %u", which);
     }
     *out_ptr = p;

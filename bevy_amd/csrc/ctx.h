@@ -389,6 +389,13 @@ struct mi_ctx {
     uint32_t an_gr_n_targets = 0, an_gr_row_end = 0, an_gr_player_end = 0;  // (n_targets: padding included; the other two as above)
     uint32_t an_gr_scale_lo = 0, an_gr_scale_hi = 0;
     bool an_have_graphs = false, an_have_graph_targets = false, an_gr_any_scale = false;
+    // ... morph weights: a pool of weight tracks of its own (mi_anim_upload_weight_tracks) and the morph targets over it and over the
+    // graphs above (mi_anim_upload_morph_targets); the layouts: kernels.h, AnimWeightArgs
+    DevBuf an_mw_tracks, an_mw_times, an_mw_values, an_mw_chunks, an_mw_bindings, an_mw_out;
+    std::vector<mi_anim_weight_track> an_mw_tracks_host;  // the pool's descriptors (the targets' upload checks against them)
+    std::vector<uint32_t> an_mw_player_graph, an_mw_player_count;  // per player: its graph (or MI_ANIM_NO_NODE); how many morph targets it has
+    uint32_t an_mw_n_chunks = 0, an_mw_n_out = 0, an_mw_player_end = 0;  // (n_out: floats of an_mw_out; player_end as above)
+    bool an_have_weight_tracks = false, an_have_morph_targets = false, an_mw_have_out = false;
     DevBuf cl_remap, cl_bind_oc, cl_bind_idx, cl_block_counts, cl_pair_cb, cl_pair_mask, cl_acc, cl_offsets, cl_indices, cl_scalars;
     // derive mode of an assignment that runs in or next to the frame kernel: which rows that frame's propagate writes (cull_frame sets them)
     const uint8_t* cl_derive_changed = nullptr;

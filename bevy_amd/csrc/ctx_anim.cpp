@@ -3,7 +3,9 @@
 // what an indexed Transform upload of the same rows is (indexed_write_begin / _end, context.cpp).  The same pair for blended
 // players: mi_anim_upload_blend_targets and mi_anim_frame_blended, which also checks and packs the frame's layers.  And a triple
 // for whole animation graphs: mi_anim_upload_graphs compiles each tree into the program k_anim_graph runs, mi_anim_upload_graph_targets
-// lays the targets out by graph, mi_anim_frame_graph hands the frame's node states over.
+// lays the targets out by graph, mi_anim_frame_graph hands the frame's node states over.  Morph weights run through the same graphs
+// from a pool of weight tracks of their own: mi_anim_upload_weight_tracks, mi_anim_upload_morph_targets (which cuts the targets into
+// the chunks k_anim_weights gives a wave each), mi_anim_frame_weights, mi_anim_download_weights.
 #include "ctx.h"
 
 using namespace mi;
@@ -382,12 +384,12 @@ int32_t mi_anim_upload_graphs(mi_ctx* ctx, uint32_t n_graphs, const mi_anim_grap
     }
     int32_t rc;
     if ((rc = ensure(ctx, ctx->an_gr_prog, prog.size() * 4))) return rc;
-    ctx->an_have_graphs = ctx->an_have_graph_targets = false;
+    ctx->an_have_graphs = ctx->an_have_graph_targets = ctx->an_have_morph_targets = false;
     if ((rc = upload(ctx, ctx->an_gr_prog.p, prog.data(), prog.size() * 4))) return rc;
     ctx->an_gr_graphs.assign(graphs, graphs + n_graphs);
     ctx->an_gr_nodes.assign(nodes, nodes + n_nodes);
     ctx->an_gr_prog_first.swap(prog_first), ctx->an_gr_prog_n.swap(prog_n);
-    ctx->an_gr_n_targets = 0;
+    ctx->an_gr_n_targets = ctx->an_mw_n_chunks = 0;
     ctx->an_have_graphs = true;
     return MI_OK;
 }
@@ -569,6 +571,182 @@ int32_t mi_anim_frame_graph(mi_ctx* ctx, uint32_t n_players, const uint32_t* fir
     HIP_TRY(ctx, launch_anim_graph(a, ctx->stream));
     indexed_write_end(ctx, w, rows);
     return MI_OK;
+}
+
+int32_t mi_anim_upload_weight_tracks(mi_ctx* ctx, uint32_t n_tracks, const mi_anim_weight_track* tracks, uint32_t n_times, const float* times, uint32_t n_values,
+                                     const float* values) {
+    ENTER(ctx);
+    if ((n_tracks && !tracks) || (n_times && !times) || (n_values && !values)) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_weight_tracks: NULL array");
+    // ---- validation: nothing of the previous pool is touched before it has passed ----
+    for (uint32_t i = 0; i < n_tracks; ++i) {
+        const mi_anim_weight_track& tr = tracks[i];
+        if (tr.interp > ANIM_CUBIC) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_weight_tracks: track %u: unknown interpolation %u", i, tr.interp);
+        if (tr.n_keys == 0) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_weight_tracks: track %u has no keys", i);
+        if (tr.n_weights == 0) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_weight_tracks: track %u has no weights", i);
+        if ((uint64_t)tr.first_time + tr.n_keys > n_times)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_weight_tracks: track %u: times [%u,+%u) exceed %u", i, tr.first_time, tr.n_keys, n_times);
+        const uint64_t per_key = (uint64_t)tr.n_weights * (tr.interp == ANIM_CUBIC ? 3u : 1u);  // (the product with n_keys may pass 2^64: divide instead)
+        if (tr.first_value > n_values || tr.n_keys > (n_values - tr.first_value) / per_key)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_weight_tracks: track %u: values [%u,+%u x %llu) exceed %u", i, tr.first_value, tr.n_keys,
+                        (unsigned long long)per_key, n_values);
+        const float* t = times + tr.first_time;
+        for (uint32_t k = 1; k < tr.n_keys; ++k)
+            if (!(t[k] > t[k - 1u])) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_weight_tracks: track %u: times not strictly ascending at key %u", i, k);
+    }
+    int32_t rc;
+    if ((rc = ensure(ctx, ctx->an_mw_tracks, (size_t)n_tracks * sizeof(mi_anim_weight_track)))) return rc;
+    if ((rc = ensure(ctx, ctx->an_mw_times, (size_t)n_times * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_mw_values, (size_t)n_values * 4))) return rc;
+    ctx->an_have_weight_tracks = ctx->an_have_morph_targets = false;
+    if ((rc = upload(ctx, ctx->an_mw_tracks.p, tracks, (size_t)n_tracks * sizeof(mi_anim_weight_track)))) return rc;
+    if ((rc = upload(ctx, ctx->an_mw_times.p, times, (size_t)n_times * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_mw_values.p, values, (size_t)n_values * 4))) return rc;
+    ctx->an_mw_tracks_host.assign(tracks, tracks + n_tracks);
+    ctx->an_mw_n_chunks = 0;
+    ctx->an_have_weight_tracks = true;
+    return MI_OK;
+}
+
+int32_t mi_anim_upload_morph_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_morph_target* targets, uint32_t n_bindings, const uint32_t* bindings,
+                                     uint32_t n_players, const uint32_t* player_graph, uint32_t n_weights_out, const float* initial_weights) {
+    ENTER(ctx);
+    if ((n_targets && !targets) || (n_bindings && !bindings) || (n_players && !player_graph))
+        return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: NULL array");
+    if (!ctx->an_have_weight_tracks || !ctx->an_have_graphs)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_upload_morph_targets before mi_anim_upload_weight_tracks and mi_anim_upload_graphs");
+    // ---- validation: nothing of the previous morph targets or of their weights is touched before it has passed ----
+    const std::vector<mi_anim_weight_track>& pool = ctx->an_mw_tracks_host;
+    for (uint32_t p = 0; p < n_players; ++p)
+        if (player_graph[p] != MI_ANIM_NO_NODE && player_graph[p] >= ctx->an_gr_graphs.size())
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: player %u: graph %u >= %zu graphs", p, player_graph[p], ctx->an_gr_graphs.size());
+    uint32_t player_end = 0;
+    uint64_t n_chunks = 0;
+    std::vector<uint32_t> c_min(n_players, 0xFFFFFFFFu), count(n_players, 0u);  // per player: the smallest n_clips of its targets; its targets
+    for (uint32_t i = 0; i < n_targets; ++i) {
+        const mi_anim_morph_target& tg = targets[i];
+        if (tg.n_weights == 0) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u has no weights", i);
+        if ((uint64_t)tg.first_weight + tg.n_weights > n_weights_out)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u: weights [%u,+%u) exceed %u", i, tg.first_weight, tg.n_weights, n_weights_out);
+        if (tg.player >= n_players) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u: player %u >= n_players = %u", i, tg.player, n_players);
+        if (player_graph[tg.player] == MI_ANIM_NO_NODE) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u: player %u has no graph", i, tg.player);
+        if (tg.n_clips == 0) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u has no clips", i);
+        if ((uint64_t)tg.first_binding + tg.n_clips > n_bindings)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u: bindings [%u,+%u) exceed %u", i, tg.first_binding, tg.n_clips, n_bindings);
+        for (uint32_t c = 0; c < tg.n_clips; ++c) {
+            const uint32_t tr = bindings[tg.first_binding + c];
+            if (tr == MI_ANIM_NO_TRACK) continue;
+            if (tr >= pool.size()) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u, clip %u: track %u >= %zu weight tracks", i, c, tr, pool.size());
+            if (pool[tr].n_weights != tg.n_weights)
+                return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: target %u, clip %u: track %u holds %u weights per key, the target has %u", i, c, tr,
+                            pool[tr].n_weights, tg.n_weights);
+        }
+        player_end = std::max(player_end, tg.player + 1u);
+        c_min[tg.player] = std::min(c_min[tg.player], tg.n_clips), ++count[tg.player];
+        n_chunks += (tg.n_weights + ANIM_WEIGHT_LANES - 1u) / ANIM_WEIGHT_LANES;
+    }
+    if (n_chunks > 0x7FFFFFFFull) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: %llu blocks of 64 weights", (unsigned long long)n_chunks);
+    for (uint32_t p = 0; p < n_players; ++p) {
+        if (!count[p]) continue;
+        const mi_anim_graph& gr = ctx->an_gr_graphs[player_graph[p]];
+        for (uint32_t k = 0; k < gr.n_nodes; ++k) {
+            const mi_anim_graph_node& nd = ctx->an_gr_nodes[gr.first_node + k];
+            if (nd.kind == MI_ANIM_NODE_CLIP && nd.clip >= c_min[p])
+                return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: graph %u, node %u: clip %u, a target of player %u has %u clips", player_graph[p], k, nd.clip, p,
+                            c_min[p]);
+        }
+    }
+    std::vector<uint32_t> order(n_targets);
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return targets[x].first_weight < targets[y].first_weight; });
+    for (uint32_t i = 1; i < n_targets; ++i) {  // (sorted by their first weight: two ranges overlap iff two neighbours do)
+        const mi_anim_morph_target &a = targets[order[i - 1u]], &b = targets[order[i]];
+        if ((uint64_t)a.first_weight + a.n_weights > b.first_weight)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_upload_morph_targets: targets %u and %u both write weight %u", order[i - 1u], order[i], b.first_weight);
+    }
+    // ---- the chunk table (kernels.h, AnimWeightArgs): by graph, by player, by first weight; a target's chunks by j0 ----
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const mi_anim_morph_target &a = targets[x], &b = targets[y];
+        return player_graph[a.player] != player_graph[b.player] ? player_graph[a.player] < player_graph[b.player] : a.player < b.player;
+    });
+    std::vector<uint32_t> chunks;
+    chunks.reserve((size_t)n_chunks * ANIM_WEIGHT_CHUNK_WORDS);
+    for (uint32_t i = 0; i < n_targets; ++i) {
+        const mi_anim_morph_target& tg = targets[order[i]];
+        const uint32_t g = player_graph[tg.player];
+        for (uint64_t j = 0; j < tg.n_weights; j += ANIM_WEIGHT_LANES) {  // (64 bits: j0 + 64 may pass 2^32)
+            const uint32_t j0 = (uint32_t)j;
+            chunks.insert(chunks.end(), {tg.first_weight + j0, j0 | (std::min(tg.n_weights - j0, ANIM_WEIGHT_LANES) - 1u), ctx->an_gr_prog_first[g], ctx->an_gr_prog_n[g],
+                                         tg.first_binding, tg.player, tg.groups_lo, tg.groups_hi});
+        }
+    }
+    std::vector<float> zeros;
+    if (!initial_weights) zeros.assign(n_weights_out, 0.0f);
+    int32_t rc;
+    if ((rc = ensure(ctx, ctx->an_mw_chunks, chunks.size() * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_mw_bindings, (size_t)n_bindings * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->an_mw_out, (size_t)n_weights_out * 4))) return rc;
+    ctx->an_have_morph_targets = ctx->an_mw_have_out = false;
+    if ((rc = upload(ctx, ctx->an_mw_chunks.p, chunks.data(), chunks.size() * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_mw_bindings.p, bindings, (size_t)n_bindings * 4))) return rc;
+    if ((rc = upload(ctx, ctx->an_mw_out.p, initial_weights ? initial_weights : zeros.data(), (size_t)n_weights_out * 4))) return rc;
+    ctx->an_mw_player_graph.assign(player_graph, player_graph + n_players);
+    ctx->an_mw_player_count.swap(count);
+    ctx->an_mw_n_chunks = (uint32_t)n_chunks;
+    ctx->an_mw_n_out = n_weights_out;
+    ctx->an_mw_player_end = player_end;
+    ctx->an_have_morph_targets = ctx->an_mw_have_out = true;
+    return MI_OK;
+}
+
+int32_t mi_anim_frame_weights(mi_ctx* ctx, uint32_t n_players, const uint32_t* first_state, uint32_t n_states, const mi_anim_node_state* states, uint32_t flags) {
+    ENTER(ctx);
+    if (flags) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_weights: flags 0x%x", flags);
+    if (!ctx->an_have_weight_tracks || !ctx->an_have_graphs || !ctx->an_have_morph_targets)
+        return fail(ctx, MI_ERR_NOT_READY, "mi_anim_frame_weights before mi_anim_upload_weight_tracks, mi_anim_upload_graphs and mi_anim_upload_morph_targets");
+    if (ctx->an_mw_player_end > n_players)
+        return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_weights: a target names player %u, n_players = %u", ctx->an_mw_player_end - 1u, n_players);
+    if ((n_players && !first_state) || (n_states && !states)) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_weights: NULL");
+    uint32_t running = 0;  // morph targets of the players that run this frame
+    for (uint32_t p = 0; p < n_players; ++p) {
+        if (first_state[p] == MI_ANIM_NO_NODE) continue;
+        if (p >= ctx->an_mw_player_graph.size() || ctx->an_mw_player_graph[p] == MI_ANIM_NO_NODE)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_weights: player %u has states and no graph", p);
+        const uint32_t nodes = ctx->an_gr_graphs[ctx->an_mw_player_graph[p]].n_nodes;
+        if ((uint64_t)first_state[p] + nodes > n_states)
+            return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_frame_weights: player %u: states [%u,+%u) exceed %u", p, first_state[p], nodes, n_states);
+        running += ctx->an_mw_player_count[p];
+    }
+    if (running == 0) return MI_OK;  // every player that has morph targets is left alone
+    // ---- one word per player and 8 bytes per state, in the pinned staging block, as mi_anim_frame_graph ----
+    void *st = nullptr, *d_st = nullptr;
+    int32_t rc = stage_alloc(ctx, ((size_t)n_players + 2u * (size_t)n_states) * 4, &st);
+    if (rc) return rc;
+    memcpy(st, first_state, (size_t)n_players * 4);
+    memcpy((uint32_t*)st + n_players, states, (size_t)n_states * 8);
+    HIP_TRY(ctx, hipHostGetDevicePointer(&d_st, st, 0));
+    AnimWeightArgs a{};
+    a.n_chunks = ctx->an_mw_n_chunks;
+    a.chunks = (const uint32_t*)ctx->an_mw_chunks.p;
+    a.bindings = (const uint32_t*)ctx->an_mw_bindings.p;
+    a.prog = (const uint32_t*)ctx->an_gr_prog.p;
+    a.tracks = (const uint32_t*)ctx->an_mw_tracks.p;
+    a.times = (const float*)ctx->an_mw_times.p;
+    a.values = (const float*)ctx->an_mw_values.p;
+    a.first_state = (const uint32_t*)d_st;
+    a.states = (const uint32_t*)d_st + n_players;
+    a.weights = (float*)ctx->an_mw_out.p;
+    HIP_TRY(ctx, launch_anim_weights(a, ctx->stream));
+    return MI_OK;
+}
+
+int32_t mi_anim_download_weights(mi_ctx* ctx, uint32_t first_weight, uint32_t n, float* out) {
+    ENTER(ctx);
+    if (!ctx->an_mw_have_out) return fail(ctx, MI_ERR_NOT_READY, "mi_anim_download_weights before mi_anim_upload_morph_targets");
+    if ((uint64_t)first_weight + n > ctx->an_mw_n_out)
+        return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_download_weights: weights [%u,+%u) exceed %u", first_weight, n, ctx->an_mw_n_out);
+    if (n == 0) return MI_OK;
+    if (!out) return fail(ctx, MI_ERR_INVALID_ARG, "mi_anim_download_weights: NULL");
+    return download(ctx, out, (const float*)ctx->an_mw_out.p + first_weight, (size_t)n * 4);
 }
 
 }  // extern "C"

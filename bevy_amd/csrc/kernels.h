@@ -955,4 +955,31 @@ struct AnimGraphArgs {
 };
 hipError_t launch_anim_graph(AnimGraphArgs a, hipStream_t stream);
 
+// One launch per mi_anim_frame_weights: a wave per CHUNK -- one morph target and ANIM_WEIGHT_LANES consecutive weights of it -- four
+// independent waves per workgroup, in the order mi_anim_upload_morph_targets laid the chunks out (by graph, by player, by target, by
+// j0; no padding).  The wave runs its player's program (prog, first_state, states: AnimGraphArgs') with everything but the values
+// wave-uniform (kernels_anim.hip).  Layouts (every index checked on the host, none again here):
+//   chunks     eight words per chunk: out0 = the output weight of lane 0 (the target's first_weight + j0); j0 | live lanes - 1 (j0
+//              is a multiple of 64); first instruction and instruction count of the player's graph; bind0; player; groups_lo, groups_hi
+//   bindings   one word per target and clip slot, as the caller handed them over: bindings[bind0 + clip] = a weight track or
+//              ANIM_NO_TRACK
+//   tracks     five words per weight track: first_time, n_keys, first_value, interp, n_weights (mi_anim_weight_track); key i's
+//              weight j is values[first_value + i n_weights + j], a CUBIC track's values[first_value + (3 i + 1) n_weights + j]
+//              between its in-tangents and its out-tangents
+constexpr uint32_t ANIM_WEIGHT_LANES = 64u, ANIM_WEIGHT_WAVES = 4u, ANIM_WEIGHT_CHUNK_WORDS = 8u, ANIM_WEIGHT_TRACK_WORDS = 5u;
+constexpr uint32_t ANIM_WEIGHT_LEVEL = ANIM_WEIGHT_LANES + 2u;  // a level of a wave's LDS stack: 64 accumulators, the weight sum, the node's weight
+struct AnimWeightArgs {
+    uint32_t n_chunks;
+    const uint32_t* chunks;
+    const uint32_t* bindings;
+    const uint32_t* prog;
+    const uint32_t* tracks;
+    const float* times;
+    const float* values;
+    const uint32_t* first_state;  // as AnimGraphArgs
+    const uint32_t* states;
+    float* weights;               // the output array
+};
+hipError_t launch_anim_weights(AnimWeightArgs a, hipStream_t stream);
+
 }  // namespace mi

@@ -19,7 +19,8 @@
 //             its ancestors; the launch zeroes the other half of the marks when asked to.
 // Arithmetic: glam_math.h (every operation rounded on its own; -ffp-contract=off); acosf / sinf are the device library's.
 // Behind k_anim_frame: k_anim_blend, the same sampling for players that blend several weighted clips (mi_anim_frame_blended), and
-// k_anim_graph, for players that run a whole tree of clip, blend and additive nodes with masks (mi_anim_frame_graph).
+// k_anim_graph, for players that run a whole tree of clip, blend and additive nodes with masks (mi_anim_frame_graph).  Last,
+// k_anim_weights: the same graphs over weight tracks, n floats per key, into an array of morph weights (mi_anim_frame_weights).
 #include "glam_math.h"
 #include "kernels.h"
 
@@ -488,7 +489,130 @@ __global__ __launch_bounds__(ANIM_GRAPH_TARGETS* ANIM_GRAPH_WAVES) void k_anim_g
         anim_graph_targets<false>(g, AnimTimes<false>{g.times, lds_times, 0u}, stack);
     }
 }
+// ---- morph weights (mi_anim_frame_weights; kernels.h, AnimWeightArgs) -----------------------------------------------------------
+// A wave owns one chunk: one morph target and 64 consecutive weights of it, lane j the weight j0 + j.  The lanes of a chunk share
+// the track, the player and the graph, so everything but the values is the same in all of them and is moved to SGPRs as it is read:
+// the chunk, the instruction, the node's state, the mask test, the track, which case of the sampling applies, u and the Hermite
+// coefficients, the weight sums.  Four such waves a workgroup, none knowing of the others: no barrier.
+//   program   k_anim_graph's, instruction for instruction.  An ENTER whose node does not count is a branch over its skip offset,
+//             so no instruction of a dead subtree is ever reached and k_anim_graph's `alive` bits have nothing left to say; whether
+//             a level has a value yet (`present`) is a bit per depth in one SGPR.
+//   sampling  one track per CLIP: the first / last / NaN cases are two scalar compares, the interval search is anim_wave_interval
+//             on the pool itself (at most two rounds of 64 probes), and then each lane loads its float of key i and of key i + 1
+//             (and of the two tangents): consecutive floats, 256 B per wave and load.
+//   stack     the accumulator of the innermost open node is one VGPR; ENTER saves it into the wave's LDS stack [level][64] with the
+//             level's weight sum and the entered node's weight as two words behind it, LEAVE takes them back and folds.  7 levels
+//             x 66 words x 4 waves: 7 392 B a workgroup.
+
+__device__ __forceinline__ uint32_t anim_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ float anim_unif(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+// anim_graph_fold for one scalar whose weight, weight sum and presence are the wave's
+__device__ __forceinline__ void anim_weight_fold(uint32_t kind, float& acc, float& wsum, bool& any, float v, float weight, bool has) {
+    if (!has) return;
+    if (!any) {
+        acc = v, wsum = weight, any = true;
+        return;
+    }
+    if (kind == ANIM_NODE_ADD) {
+        acc = acc + v * weight;
+        return;
+    }
+    wsum = wsum + weight;
+    const float u = f_div(weight, wsum);
+    acc = acc + (v - acc) * u;
+}
+
+// The lane's weight of track `tr` (five wave-uniform words) at x; anim_sample's arithmetic for one float.
+__device__ __forceinline__ float anim_weight_sample(const AnimWeightArgs& a, const uint32_t* tr, float x, uint32_t j, bool live, uint32_t lane) {
+    const uint32_t ft = anim_uni(tr[0]), k = anim_uni(tr[1]), fv = anim_uni(tr[2]), interp = anim_uni(tr[3]), nw = anim_uni(tr[4]);
+    const AnimTimes<false> ts{a.times, nullptr, 0u};
+    const bool first = k == 1u || !(x > anim_unif(ts.at(ft)));  // (a NaN seek time: the first key)
+    const bool last = !first && x >= anim_unif(ts.at(ft + k - 1u));
+    const bool need = !first && !last;  // strictly inside the track
+    const uint32_t i = need ? anim_uni(anim_wave_interval(ts, ft, k, x, lane)) : (last ? k - 1u : 0u);
+    const uint32_t stride = interp == ANIM_CUBIC ? 3u * nw : nw, value_at = interp == ANIM_CUBIC ? nw : 0u;
+    const float* key = a.values + ((size_t)fv + (size_t)i * stride + j);  // the lane's float of key i: [in-tangent,] value [, out-tangent]
+    float out = 0.0f;
+    if (live) out = key[value_at];
+    if (!need || interp == ANIM_STEP) return out;
+    const float ti = anim_unif(ts.at(ft + i));
+    if (x == ti) return out;  // exactly on a key
+    const float dt = anim_unif(ts.at(ft + i + 1u)) - ti;
+    const float u = f_div(x - ti, dt);
+    const float va = out;
+    float vb = 0.0f;
+    if (live) vb = key[(size_t)stride + value_at];
+    if (interp == ANIM_LINEAR) return va + (vb - va) * u;
+    float tan_out = 0.0f, tan_in = 0.0f;
+    if (live) tan_out = key[2u * (size_t)nw], tan_in = key[stride];
+    const float u2 = u * u, u3 = u2 * u;
+    const float h00 = (2.0f * u3 - 3.0f * u2) + 1.0f, h10 = dt * ((u3 - 2.0f * u2) + u), h01 = 3.0f * u2 - 2.0f * u3, h11 = dt * (u3 - u2);
+    return ((h00 * va + h10 * tan_out) + h01 * vb) + h11 * tan_in;
+}
+
+__global__ __launch_bounds__(ANIM_WEIGHT_LANES* ANIM_WEIGHT_WAVES) void k_anim_weights(AnimWeightArgs a) {
+    __shared__ float stacks[ANIM_WEIGHT_WAVES * ANIM_GRAPH_LEVELS * ANIM_WEIGHT_LEVEL];
+    const uint32_t wave = anim_uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t chunk = blockIdx.x * ANIM_WEIGHT_WAVES + wave;
+    if (chunk >= a.n_chunks) return;  // (whole waves)
+    const uint4 c0 = reinterpret_cast<const uint4*>(a.chunks)[2u * (size_t)chunk], c1 = reinterpret_cast<const uint4*>(a.chunks)[2u * (size_t)chunk + 1u];
+    const uint32_t first = anim_uni(a.first_state[anim_uni(c1.y)]);
+    if (first == ANIM_GRAPH_NO_NODE) return;  // the player is left alone
+    const uint32_t out0 = anim_uni(c0.x), j = (anim_uni(c0.y) & ~63u) + lane, prog0 = anim_uni(c0.z), prog_n = anim_uni(c0.w), bind0 = anim_uni(c1.x);
+    const bool live = lane <= (anim_uni(c0.y) & 63u);
+    const uint64_t groups = (uint64_t)anim_uni(c1.z) | (uint64_t)anim_uni(c1.w) << 32;
+    float* stack = stacks + wave * (ANIM_GRAPH_LEVELS * ANIM_WEIGHT_LEVEL);
+    float acc = 0.0f, wsum = 0.0f;
+    uint32_t present = 0u;  // bit d: the open node of depth d has a value (bit 0: the result)
+    for (uint32_t pc = 0; pc < prog_n;) {
+        const uint4 in = reinterpret_cast<const uint4*>(a.prog)[prog0 + pc];
+        const uint32_t head = anim_uni(in.x);
+        const uint32_t op = head & 3u, d = (head >> 2) & 15u, into = (head >> 6) & 3u, node = (head >> 8) & 0xFFu;
+        if (op == ANIM_OP_LEAVE) {  // the open node of depth d is complete: fold it into the one saved at level d - 1
+            const float* c = stack + (d - 1u) * ANIM_WEIGHT_LEVEL;
+            float outer = c[lane], outer_wsum = anim_unif(c[ANIM_WEIGHT_LANES]);
+            bool outer_any = (present >> (d - 1u)) & 1u;
+            anim_weight_fold(into, outer, outer_wsum, outer_any, acc, anim_unif(c[ANIM_WEIGHT_LANES + 1u]), (present >> d) & 1u);
+            acc = outer, wsum = outer_wsum;
+            present = (present & ~(3u << (d - 1u))) | ((outer_any ? 1u : 0u) << (d - 1u));
+            ++pc;
+            continue;
+        }
+        const uint32_t* st = a.states + 2ull * ((uint64_t)first + node);
+        const float weight = __uint_as_float(anim_uni(st[0])), x = __uint_as_float(anim_uni(st[1]));
+        const uint64_t mask = (uint64_t)anim_uni(in.z) | (uint64_t)anim_uni(in.w) << 32;
+        const bool on = weight > 0.0f && (mask & groups) == 0;  // (a NaN weight: not on; the node around it is on, or this one is not reached)
+        if (op == ANIM_OP_ENTER) {
+            if (!on) {  // the subtree is dead
+                pc += head >> 16;
+                continue;
+            }
+            float* c = stack + (d - 1u) * ANIM_WEIGHT_LEVEL;
+            c[lane] = acc;
+            c[ANIM_WEIGHT_LANES] = wsum, c[ANIM_WEIGHT_LANES + 1u] = weight;  // (every lane the same two words)
+            present &= ~(1u << d);
+            ++pc;
+            continue;
+        }
+        const uint32_t track = on ? anim_uni(a.bindings[(size_t)bind0 + anim_uni(in.y)]) : ANIM_NO_TRACK;  // ANIM_OP_CLIP
+        if (track != ANIM_NO_TRACK) {
+            const float v = anim_weight_sample(a, a.tracks + (size_t)ANIM_WEIGHT_TRACK_WORDS * track, x, j, live, lane);
+            bool any = (present >> (d - 1u)) & 1u;
+            anim_weight_fold(into, acc, wsum, any, v, weight, true);
+            present |= (any ? 1u : 0u) << (d - 1u);
+        }
+        ++pc;
+    }
+    if ((present & 1u) && live) a.weights[(size_t)out0 + lane] = acc;  // (an absent root: the weights keep what they held)
+}
 }  // namespace
+
+hipError_t launch_anim_weights(AnimWeightArgs a, hipStream_t stream) {
+    if (a.n_chunks == 0) return hipSuccess;
+    MI_LAUNCH(k_anim_weights, dim3((a.n_chunks + ANIM_WEIGHT_WAVES - 1u) / ANIM_WEIGHT_WAVES), dim3(ANIM_WEIGHT_LANES * ANIM_WEIGHT_WAVES), 0, stream, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_anim_graph(AnimGraphArgs a, hipStream_t stream) {
     if (a.n_targets == 0) return hipSuccess;

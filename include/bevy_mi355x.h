@@ -879,8 +879,9 @@ int32_t mi_skin_download_bounds(mi_ctx* ctx, uint32_t first_skin, uint32_t n, fl
  * one float per player -- its seek time -- instead of being sampled on a core and uploaded, 40 bytes per joint and frame.
  * Players that blend one level of weighted clips -- a transition's crossfade, a flat blend node over clip nodes -- go through
  * mi_anim_upload_blend_targets / mi_anim_frame_blended below; players whose graph is more than that -- nested blend nodes,
- * additive nodes, masks -- through mi_anim_upload_graphs / mi_anim_upload_graph_targets / mi_anim_frame_graph behind them.  Out of
- * scope: morph weights, and advancing the players' clocks.  The host advances the seek times and the weights.
+ * additive nodes, masks -- through mi_anim_upload_graphs / mi_anim_upload_graph_targets / mi_anim_frame_graph behind them, and
+ * morph weights through the same graphs by mi_anim_frame_weights, last in this block.  Out of scope: advancing the players' clocks.
+ * The host advances the seek times and the weights.
  * The reference sources were not at hand when this was written: the arithmetic stated here is the library's definition, in glam's
  * operation order as everywhere else, and has NOT been pinned against a run of the reference.
  *
@@ -1069,6 +1070,68 @@ int32_t mi_anim_upload_graph_targets(mi_ctx* ctx, uint32_t n_targets, const mi_a
 int32_t mi_anim_frame_graph(mi_ctx* ctx, uint32_t n_players, const uint32_t* first_state, uint32_t n_states, const mi_anim_node_state* states,
                             uint32_t flags);
 
+/* Morph weights: what animate_targets writes into MorphWeights -- weight tracks, n floats per key, run through the player's
+ * AnimationGraph -- into one array of floats on the device.  A pool and a state of their own beside everything above; only the
+ * graphs (mi_anim_upload_graphs) are shared.
+ *
+ *   mi_anim_upload_weight_tracks  replaces the pool of weight tracks and drops the morph targets.  Independent of
+ *                    mi_anim_upload_tracks in both directions: neither call touches the other's pool or targets.  A track is
+ *                    n_keys key times times[first_time ..] and, per key, n_weights floats from values[first_value ..]; a
+ *                    MI_ANIM_CUBIC track holds 3 n_weights floats per key, in glTF order: n_weights in-tangents, n_weights values,
+ *                    n_weights out-tangents.  Checked as mi_anim_upload_tracks checks, MI_ERR_INVALID_ARG with a message and the
+ *                    previous state left in place: every range inside its pool; n_keys >= 1; n_weights >= 1; times strictly
+ *                    ascending within a track; a known interpolation.
+ *   mi_anim_upload_morph_targets  replaces the morph targets (mi_anim_upload_weight_tracks and mi_anim_upload_graphs drop them) and
+ *                    allocates the output array, n_weights_out floats filled from initial_weights (NULL: zeros).  A target writes
+ *                    weights[first_weight, first_weight + n_weights) for player `player`; bindings[first_binding + c], c < n_clips,
+ *                    is the weight track clip slot c of the player's graph animates on it, or MI_ANIM_NO_TRACK.  groups_lo /
+ *                    groups_hi and player_graph as mi_anim_upload_graph_targets'; the graphs are the ones mi_anim_upload_graphs
+ *                    holds.  Checked, MI_ERR_INVALID_ARG with a message and the previous state left in place: output ranges inside
+ *                    the array and pairwise disjoint; n_weights >= 1; n_clips >= 1; binding ranges inside the array; every bound
+ *                    track in range and of the target's n_weights; player < n_players; the player's graph exists; every CLIP
+ *                    node's clip below the smallest n_clips of the player's targets.  MI_ERR_NOT_READY before the weight tracks
+ *                    and the graphs.
+ *   mi_anim_frame_weights  one kernel launch, asynchronous.  first_state and states exactly as mi_anim_frame_graph's, with its
+ *                    checks and its MI_ERR_NOT_READY rules (here: before the weight tracks, the graphs and the morph targets);
+ *                    flags: pass 0.  A player with MI_ANIM_NO_NODE is left alone.  The call writes the output array and nothing
+ *                    else -- no Transform column, change byte, mark or summary -- and may stand before or after the other
+ *                    animation calls of a frame.  One word per player and 8 bytes per state travel in the pinned staging block.
+ *   mi_anim_download_weights  weights [first_weight, first_weight + n) of the output array, behind everything enqueued; before the
+ *                    first frame, the initial weights.  MI_ERR_NOT_READY before mi_anim_upload_morph_targets.  The array stays on
+ *                    the device as MI_BUF_MORPH_WEIGHTS (mi_device_buffer).
+ * Each weight is a scalar that follows the rules above for one translation component, every operation rounded on its own: the
+ * sampling's first / last / NaN / exact-key cases, LINEAR a + (b - a) * u, the Hermite form with d (a = values[i][j], out_i and
+ * in_{i+1} the tangents of the same j), no normalize; and the graph's: absent nodes, BLEND by cumulative weight, ADD acc + v * w, an
+ * inner node with no present child absent.  A target whose root is absent is not written: its weights keep what they held.  A root
+ * CLIP serves single-clip players and a root BLEND crossfades, so this one call serves all three forms; a weight track of
+ * n_weights = 3 gives, bit for bit, the translation mi_anim_frame_graph writes for the same keys, graph and states.
+ * Per frame a block of 64 weights reads 32 bytes of its own, its graph's program and states, 20 bytes per track and two keys' floats
+ * (four for CUBIC) per lane, and writes 4 bytes per weight.
+ * Cost (profiles/r13_weights/ab.md, one run, wall clock, the host's share included): 1 000 rigs of one 52-weight target under
+ * add(blend(blend(c0,c1),c2),c3) 49 us, 40 000 rigs 274 us; numpy evaluation on a core + one hipMemcpy of the result 393 us and
+ * 16.6 ms; mi_anim_frame_graph over the same scalars as translation tracks 60 and 410 us.  Not measured: the kernel on its own,
+ * cubic and long tracks, targets of few weights (a target idles the lanes of its last block of 64 it does not fill). */
+typedef struct mi_anim_weight_track {
+    uint32_t first_time, n_keys;  /* times[first_time, first_time + n_keys) of THIS pool */
+    uint32_t first_value;         /* n_keys x n_weights floats; MI_ANIM_CUBIC: n_keys x 3 x n_weights (in-tangents, values, out-tangents) */
+    uint32_t interp;              /* MI_ANIM_STEP / _LINEAR / _CUBIC */
+    uint32_t n_weights;           /* >= 1 */
+} mi_anim_weight_track;
+typedef struct mi_anim_morph_target {
+    uint32_t player;
+    uint32_t first_weight, n_weights;  /* writes weights[first_weight, first_weight + n_weights) of the output array */
+    uint32_t first_binding, n_clips;   /* bindings[first_binding + c]: the weight track clip slot c animates here, or MI_ANIM_NO_TRACK */
+    uint32_t groups_lo, groups_hi;     /* mask groups, as mi_anim_graph_target */
+} mi_anim_morph_target;
+int32_t mi_anim_upload_weight_tracks(mi_ctx* ctx, uint32_t n_tracks, const mi_anim_weight_track* tracks, uint32_t n_times, const float* times,
+                                     uint32_t n_values, const float* values);
+int32_t mi_anim_upload_morph_targets(mi_ctx* ctx, uint32_t n_targets, const mi_anim_morph_target* targets, uint32_t n_bindings,
+                                     const uint32_t* bindings, uint32_t n_players, const uint32_t* player_graph, uint32_t n_weights_out,
+                                     const float* initial_weights);
+int32_t mi_anim_frame_weights(mi_ctx* ctx, uint32_t n_players, const uint32_t* first_state, uint32_t n_states, const mi_anim_node_state* states,
+                              uint32_t flags);
+int32_t mi_anim_download_weights(mi_ctx* ctx, uint32_t first_weight, uint32_t n, float* out);
+
 /* ======================================================================================= */
 /* camera helpers (pure host code; what update_frusta computes, visibility/mod.rs:627-636)   */
 /* ======================================================================================= */
@@ -1184,6 +1247,7 @@ int32_t mi_exchange_download(mi_ctx* ctx, void* out_host, uint64_t bytes);
 #define MI_BUF_TRANSLATION 14             /* the Transform columns: 12 / 16 / 12 bytes per row; valid until the next mi_columns_resize */
 #define MI_BUF_ROTATION 15
 #define MI_BUF_SCALE 16
+#define MI_BUF_MORPH_WEIGHTS 17           /* n_weights_out floats; valid until the next mi_anim_upload_morph_targets */
 int32_t mi_device_buffer(mi_ctx* ctx, uint32_t which, void** out_device_ptr, uint64_t* out_bytes);
 
 /* Bench / test instrumentation (HIP-event timers, the per-kernel profile, planner and trace hooks) is declared in

@@ -27,7 +27,7 @@ STRUCT_RUST = {"mi_ctx": "MiCtx", "mi_view": "MiView", "mi_cluster_view": "MiClu
                "mi_hierarchy_advice": "MiHierarchyAdvice", "mi_skin": "MiSkin", "mi_joint_aabb": "MiJointAabb", "mi_anim_track": "MiAnimTrack", "mi_anim_target": "MiAnimTarget",
                "mi_anim_binding": "MiAnimBinding", "mi_anim_blend_target": "MiAnimBlendTarget", "mi_anim_layer": "MiAnimLayer",
                "mi_anim_graph_node": "MiAnimGraphNode", "mi_anim_graph": "MiAnimGraph", "mi_anim_graph_target": "MiAnimGraphTarget",
-               "mi_anim_node_state": "MiAnimNodeState"}
+               "mi_anim_node_state": "MiAnimNodeState", "mi_anim_weight_track": "MiAnimWeightTrack", "mi_anim_morph_target": "MiAnimMorphTarget"}
 
 
 def strip_comments(src):

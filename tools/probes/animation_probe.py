@@ -7,7 +7,10 @@ profiles/r11_blend/ab.md: --blend, the crossfade scene -- every rig's player wit
 and blending + mi_upload_transforms_indexed); --blend-deviation, the float32 run of test_gpu_anim_blend's reference (no GPU needed).
 profiles/r12_graph/ab.md: --graph, (a) a nested graph with an additive clip through mi_anim_frame_graph against its numpy evaluation +
 mi_upload_transforms_indexed, (b) a flat two-clip graph through mi_anim_frame_graph against mi_anim_frame_blended on the same work;
---graph-deviation, the float32 run of test_gpu_anim_graph's reference per shape (no GPU needed)."""
+--graph-deviation, the float32 run of test_gpu_anim_graph's reference per shape (no GPU needed).
+profiles/r13_weights/ab.md: --weights, N rigs with one target of 52 morph weights each through mi_anim_frame_weights, under the seven-node
+graph of --graph and under a root CLIP, against (1) numpy evaluation on a core + one hipMemcpy of the result into the device array and
+(2) mi_anim_frame_graph over 18 translation-only targets per rig (54 scalars: the same work laid out a lane per target)."""
 import argparse
 import os
 import sys
@@ -319,6 +322,78 @@ def graph_ab(rigs, reps):
     print(f"      anim_frame_blended, the same two layers + propagate                  {quartiles(took['blended'])}")
 
 
+MORPHS = 52
+
+
+def weights_ab(rigs, reps):
+    """Four clips of one 52-weight linear track each over KEYS times, bindings shared by every rig; the twin scene for anim_frame_graph
+    cuts the same keys into 18 translation tracks per clip (the last padded).  No propagate on either side: weights need none."""
+    import ctypes as C
+    rng = np.random.default_rng(rigs)
+    rows = (MORPHS + 2) // 3
+    times = np.tile(np.linspace(0, 1, KEYS).astype(F32), 4)
+    keys = rng.normal(0, 1, (4, KEYS, 3 * rows)).astype(F32)  # [clip][key][scalar]; the weights are the first 52 scalars of a key
+    w_tracks = np.array([(KEYS * c, KEYS, c * KEYS * MORPHS, B.ANIM_LINEAR, MORPHS) for c in range(4)], B.ANIM_WEIGHT_TRACK_DTYPE)
+    w_values = np.concatenate([keys[c, :, :MORPHS].reshape(-1) for c in range(4)])
+    t_tracks = np.array([(KEYS * c, KEYS, (c * rows + j) * KEYS * 3, B.ANIM_TRANSLATION | B.ANIM_LINEAR) for c in range(4) for j in range(rows)], B.ANIM_TRACK_DTYPE)
+    t_values = np.concatenate([keys[c, :, 3 * j:3 * j + 3].reshape(-1) for c in range(4) for j in range(rows)])
+    morph = np.zeros(rigs, B.ANIM_MORPH_TARGET_DTYPE)
+    morph["player"], morph["first_weight"], morph["n_weights"], morph["n_clips"] = np.arange(rigs), MORPHS * np.arange(rigs), MORPHS, 4
+    n = rigs * rows
+    targets, bindings = np.zeros(n, B.ANIM_GRAPH_TARGET_DTYPE), np.full(4 * rows, B.ANIM_NO_TRACK, B.ANIM_BINDING_DTYPE)
+    targets["row"], targets["player"], targets["first_binding"], targets["n_clips"] = np.arange(n), np.arange(n) // rows, 4 * (np.arange(n) % rows), 4
+    bindings["track_t"] = rows * (np.arange(4 * rows) % 4) + np.arange(4 * rows) // 4
+    nodes = np.array([(*nd, 0, 0) for nd in DEEP + [(0, 0xFFFFFFFF, 0)]], B.ANIM_GRAPH_NODE_DTYPE)
+    graphs = np.array([(0, len(DEEP)), (len(DEEP), 1)], B.ANIM_GRAPH_DTYPE)
+    deep, single = np.zeros(7 * rigs, B.ANIM_NODE_STATE_DTYPE), np.zeros(rigs, B.ANIM_NODE_STATE_DTYPE)
+    deep["weight"], single["weight"] = np.tile(np.array([1, 0.8, 0.6, 0.3, 0.7, 0.5, 0.25], F32), rigs), 1
+    hip = C.CDLL("libamdhip64.so")
+    took = {}
+    with B.Context() as ctx:
+        ctx.resize(n)
+        ctx.upload_transforms(np.zeros(3 * n, F32), np.tile(np.array([0, 0, 0, 1], F32), n), np.ones(3 * n, F32))
+        ctx.propagate()
+        ctx.anim_upload_tracks(t_tracks, times, t_values)
+        ctx.anim_upload_weight_tracks(w_tracks, times, w_values)
+        ctx.anim_upload_graphs(graphs, nodes)
+
+        def timed(key, fn, keep):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            if keep:
+                took.setdefault(key, []).append(time.perf_counter() - t0)
+
+        def host_path(x, which, out_ptr):
+            t = times[:KEYS]
+            i = np.clip(np.searchsorted(t, x, side="right") - 1, 0, KEYS - 2)  # [rigs, 4]
+            u = ((x - t[i]) / (t[i + 1] - t[i])).astype(F32)[:, :, None]
+            v = [keys[c, i[:, c], :MORPHS] + (keys[c, i[:, c] + 1, :MORPHS] - keys[c, i[:, c], :MORPHS]) * u[:, c] for c in range(4 if which == 0 else 1)]
+            if which == 0:
+                inner = v[0] + (v[1] - v[0]) * F32(0.7)
+                v[0] = (inner + (v[2] - inner) * F32(0.5 / 1.1)) + v[3] * F32(0.25)
+            out = np.ascontiguousarray(v[0], F32)
+            assert hip.hipMemcpy(C.c_void_p(out_ptr), C.c_void_p(out.ctypes.data), C.c_size_t(out.nbytes), 1) == 0
+
+        for which, first, states, name in ((0, 7 * np.arange(rigs), deep, "seven nodes"), (1, np.arange(rigs), single, "root CLIP")):
+            ctx.anim_upload_morph_targets(morph, np.arange(4), np.full(rigs, which, U32), MORPHS * rigs)
+            ctx.anim_upload_graph_targets(targets, bindings, np.full(rigs, which, U32))
+            out_ptr = ctx.device_buffer(B.BUF_MORPH_WEIGHTS)[0]
+            for rep in range(reps + 5):  # (five warm-up frames; the three paths alternate)
+                x = rng.uniform(0.01, 0.99, (rigs, 4)).astype(F32)
+                if which == 0:
+                    deep["seek_time"].reshape(rigs, 7)[:, [3, 4, 5, 6]] = x
+                else:
+                    single["seek_time"] = x[:, 0]
+                timed(name + ": anim_frame_weights", lambda: ctx.anim_frame_weights(first, states), rep >= 5)
+                timed(name + ": numpy evaluation + one hipMemcpy", lambda: host_path(x, which, out_ptr), rep >= 5)
+                timed(name + f": anim_frame_graph, {rows} translation targets a rig", lambda: ctx.anim_frame_graph(first, states), rep >= 5)
+    print(f"{rigs} rigs x {MORPHS} morph weights, {reps} frames, wall clock around synchronize:")
+    for key, xs in took.items():
+        print(f"  {key:75s} {quartiles(xs)}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--deviation", action="store_true")
@@ -328,11 +403,15 @@ if __name__ == "__main__":
     ap.add_argument("--blend-deviation", action="store_true")
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--graph-deviation", action="store_true")
+    ap.add_argument("--weights", action="store_true")
     a = ap.parse_args()
     if a.deviation:
         deviation()
     elif a.graph_deviation:
         graph_deviation()
+    elif a.weights:
+        for rigs in a.rigs.split(","):
+            weights_ab(int(rigs), a.reps)
     elif a.graph:
         for rigs in a.rigs.split(","):
             graph_ab(int(rigs), a.reps)
